@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: Gaussian samples/sec of the red-black Gibbs sweep on a 512^3 DMDA (BASELINE.json).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+
+--steps K is the number of timed steps; "ms_per_step" in the JSON line is the time of one.  The timed steps run the chain
+from x0 = 0 with noise counters 0..K-1 whatever the warm-up did, so the same arguments give the same result; with
+--dump-outputs that result (the sample y after the last timed step) is written to DIR as .npy files, see dump_outputs().
 
 N > 1: one rank per GPU.  Under torch.distributed.run (WORLD_SIZE set) this process IS a rank; started plainly it
 spawns `python -m torch.distributed.run --nproc-per-node N bench.py ...` itself before touching a GPU and relays
@@ -396,6 +400,50 @@ def unstructured_dist_secondary(rank: int, world: int, transport, share: bool, r
     return res
 
 
+DUMP_FULL_MAX = 1 << 22  # unknowns: up to 32 MB of f64 the whole sample is written
+DUMP_SAMPLE = 1 << 21  # above that: this many entries at fixed seeded positions (16 MB of values + 16 MB of indices)
+
+
+def dump_outputs(dirpath: str, g, y, n: int, rank: int, world: int) -> dict:
+    """--dump-outputs: what the timed steps computed, as the caller of the sampler receives it -- the sample y after the
+    last timed step, in the natural (i fastest) order of the whole n^3 grid, f64.  Up to DUMP_FULL_MAX unknowns:
+    y.npy holds every entry.  Above: y_sample.npy holds DUMP_SAMPLE entries at positions drawn once from a fixed seed
+    (the same for every run with the same --grid-n) and y_sample_index.npy those positions (exact in f64).  Collective
+    over all ranks (each contributes its z-slab); rank 0 writes.  Returns {name: shape} of the files written."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+
+    from parmgmc_amd.slab import slab_cuts
+
+    total = n ** 3
+    off = slab_cuts(n, world)[rank] * n * n  # the first global index of this rank's slab
+    nat = g.from_cvec(y)
+    if total <= DUMP_FULL_MAX:
+        idx = None
+        mine = nat.cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0x5EED).choice(total, size=DUMP_SAMPLE, replace=False))
+        sel = idx[(idx >= off) & (idx < off + g.n)] - off
+        mine = nat[torch.as_tensor(sel, device=nat.device)].cpu().numpy()
+    del nat
+    parts = [None] * world
+    if world > 1:
+        dist.all_gather_object(parts, mine)
+    else:
+        parts[0] = mine
+    if rank != 0:
+        return {}
+    vals = np.ascontiguousarray(np.concatenate(parts), dtype=np.float64)  # slabs are contiguous in z: rank order = index order
+    assert vals.size == (total if idx is None else DUMP_SAMPLE), vals.size
+    out = Path(dirpath)
+    out.mkdir(parents=True, exist_ok=True)
+    arrays = {"y": vals} if idx is None else {"y_sample": vals, "y_sample_index": idx.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(out / f"{name}.npy", a)
+    return {name: list(a.shape) for name, a in arrays.items()}
+
+
 def spawn_ranks(n: int, argv: list) -> int:
     """`python bench.py --gpus N` with N > 1 and no torchrun environment: start N fresh ranks (one per GPU) as a child
     `python -m torch.distributed.run` BEFORE this process imports torch or touches a GPU, pass their output through
@@ -472,7 +520,10 @@ def main() -> None:
     ap.add_argument("--no-settle", action="store_true", help="skip the clock-settle phase")
     ap.add_argument("--mgmc-n", type=int, default=513, help="grid of the distributed V-cycle line (2^k + 1)")
     ap.add_argument("--mgmc-levels", type=int, default=6)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the sample they computed as DIR/<name>.npy (see dump_outputs())")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus, sys.argv[1:]))
@@ -563,7 +614,10 @@ def main() -> None:
             err = f"warm-up: {type(e).__name__}: {e}"
         if not agree(err is None):  # nobody enters the timed region unless everybody can
             return dict(smp=smp, err=err or "warm-up failed on another rank", ok=False)
-        timed_from = ctr
+        # the timed region starts the chain afresh (x0 = 0, noise counters from 0): what it computes then depends on the
+        # arguments alone, not on how many sweeps the adaptive settle phase took
+        y.zero_()
+        ctr = timed_from = 0
         barrier()
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
@@ -639,6 +693,7 @@ def main() -> None:
         sys.exit(4)
     smp, g, y, b, dt, dev_ms, finite, halo_check = (res[k] for k in ("smp", "g", "y", "b", "dt", "dev_ms", "finite", "halo_check"))
     used_transport = smp.transport
+    dumped = dump_outputs(args.dump_outputs, g, y, n, rank, world) if args.dump_outputs else None
 
     if rank == 0:
         N_total = n * n * n
@@ -673,6 +728,8 @@ def main() -> None:
                 out["roofline"]["stream_ceiling"] = sc
             except Exception as e:  # never allowed to cost the headline line
                 out["roofline"]["stream_ceiling"] = {"error": f"{type(e).__name__}: {e}"}
+        if dumped:
+            out["dump_outputs"] = {"dir": str(Path(args.dump_outputs).resolve()), "arrays": dumped}
         if halo_check is not None:
             out["halo_check"] = halo_check
         if res.get("ranks"):

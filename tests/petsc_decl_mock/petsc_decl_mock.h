@@ -155,8 +155,8 @@ PetscErrorCode PetscOptionsGetBool(PetscOptions, const char[], const char[], Pet
 PetscErrorCode PetscViewerASCIIPrintf(PetscViewer, const char[], ...);
 PetscErrorCode PetscRandomGetSeed(PetscRandom, PetscInt64 *);
 PetscErrorCode PetscRandomDestroy(PetscRandom *);
-/* what the reference's examples ex3.c / ex5.c call besides the adapter's own needs (tests/test_adapter_syntax.py compiles them
-   UNCHANGED from /root/reference against these declarations and the MCSOR binding of adapter/mc_sor_hip.c) */
+/* what the reference's examples ex3.c / ex5.c call besides the adapter's own needs (tests/test_adapter_syntax.py checks that
+   every name of tests/golden/reference_example_calls.json is declared here or defined by adapter/mc_sor_hip.c) */
 PetscErrorCode PetscInitialize(int *, char ***, const char[], const char[]);
 PetscErrorCode PetscFinalize(void);
 PetscErrorCode PetscObjectSetName(PetscObject, const char[]);

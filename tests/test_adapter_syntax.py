@@ -8,6 +8,7 @@ here: the image has no PETSc.  What CAN be checked without it:
   * every pmg_* function they call is declared in include/parmgmc_hip.h and exported by the library;
   * without -DPARMGMC_HIP_HAVE_PETSC they are empty translation units.
 Behaviour against a real PETSc stays untested (stated in DESIGN.md)."""
+import json
 import re
 import shutil
 import subprocess
@@ -18,8 +19,9 @@ import pytest
 ROOT = Path(__file__).resolve().parent.parent
 ADAPTER = ROOT / "adapter"
 FILES = [ADAPTER / "pc_hipgibbs.c", ADAPTER / "pc_hipgamgmc.c", ADAPTER / "pc_hipparsor.c", ADAPTER / "pc_hipwoodbury.c", ADAPTER / "mc_sor_hip.c"]
-REFERENCE = Path("/root/reference")  # present in the build container only; never on the GPU box
 GCC = shutil.which("gcc")
+# the ten functions of the reference's MCSOR interface (include/parmgmc/mc_sor.h:21-30)
+MCSOR_INTERFACE = ("MCSORCreate", "MCSORSetUp", "MCSORDestroy", "MCSORApply", "MCSORSetOmega", "MCSORSetSweepType", "MCSORGetSweepType", "MCSORGetISColoring", "MCSORGetNumColors", "MCSORBuildLRCCorrection")
 INC = ["-I", str(ROOT / "tests" / "petsc_decl_mock"), "-I", str(ROOT / "include"), "-I", "/opt/rocm/include", "-I", str(ADAPTER), "-D__HIP_PLATFORM_AMD__"]
 
 
@@ -103,29 +105,35 @@ def test_mcsor_binding_and_the_reference_option_keys():
 
 @pytest.mark.parametrize("idx", ["32", "64"])
 def test_mcsor_binding_matches_the_reference_header(idx):
-    """adapter/mc_sor_hip.c compiled with the REFERENCE's own <parmgmc/mc_sor.h> and <parmgmc/parmgmc.h> in front of the
-    declaration mock: a definition that disagrees with the reference's prototype is a compile error (read in place under
-    /root/reference; nothing of it is in this repository)"""
-    if not GCC or not (REFERENCE / "include" / "parmgmc" / "mc_sor.h").exists():
-        pytest.skip("needs gcc and /root/reference (build container only)")
+    """adapter/mc_sor_hip.c compiled with the declarations of the reference's MCSOR interface (include/parmgmc/mc_sor.h:
+    17-30, transcribed in tests/petsc_decl_mock/parmgmc/mc_sor.h, which the binding's #include <parmgmc/mc_sor.h> finds
+    first): a definition that disagrees with the reference's prototype is a compile error"""
+    if not GCC:
+        pytest.skip("no gcc")
+    hdr = ROOT / "tests" / "petsc_decl_mock" / "parmgmc" / "mc_sor.h"
+    declared = set(re.findall(r"PETSC_EXTERN PetscErrorCode (MCSOR[A-Za-z]+)\(", hdr.read_text()))
+    assert declared == set(MCSOR_INTERFACE), declared ^ set(MCSOR_INTERFACE)
     extra = ["-DPETSC_DECL_MOCK_64BIT_INDICES"] if idx == "64" else []
-    r = subprocess.run([GCC, "-std=gnu11", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-DPARMGMC_HIP_HAVE_PETSC", *extra, "-I", str(REFERENCE / "include"), *INC, str(ADAPTER / "mc_sor_hip.c")], capture_output=True, text=True)
+    r = subprocess.run([GCC, "-std=gnu11", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-DPARMGMC_HIP_HAVE_PETSC", *extra, *INC, str(ADAPTER / "mc_sor_hip.c")], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
 
 
 @pytest.mark.parametrize("example", ["ex3.c", "ex5.c"])
-def test_reference_examples_compile_unchanged_against_the_binding(example):
+def test_reference_example_calls_resolve_against_the_binding(example, tmp_path):
     """examples/ex3.c (MCSOR inside a PCSHELL: the route BASELINE's north star names) and examples/ex5.c (symmetric =
-    forward o backward) of the reference, UNCHANGED, read in place: valid C against the reference's own parmgmc headers +
-    the PETSc declaration mock, i.e. every MCSOR* / PETSc call they make has the signature the binding and the mock declare"""
-    src = REFERENCE / "examples" / example
-    if not GCC or not src.exists():
-        pytest.skip("needs gcc and /root/reference (build container only)")
-    r = subprocess.run([GCC, "-std=gnu11", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", "-I", str(REFERENCE / "include"), "-I", str(ROOT / "tests" / "petsc_decl_mock"), str(src)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr
-    calls = set(re.findall(r"\b(MCSOR[A-Za-z]+)\(", src.read_text()))
+    forward o backward) of the reference: every MCSOR* function they call is defined by the binding, and every PETSc
+    function they call is declared by the declaration mock -- for both index widths, checked by compiling a translation
+    unit that takes the address of each.  The names are a fixture (tests/golden/reference_example_calls.json)."""
+    calls = json.loads((ROOT / "tests" / "golden" / "reference_example_calls.json").read_text())[example]
     binding = (ADAPTER / "mc_sor_hip.c").read_text()
-    assert calls and all(f"PetscErrorCode {c}(" in binding for c in calls), calls
+    assert calls["mcsor"] and all(c in MCSOR_INTERFACE and f"PetscErrorCode {c}(" in binding for c in calls["mcsor"]), calls["mcsor"]
+    if not GCC:
+        pytest.skip("no gcc")
+    tu = tmp_path / "calls.c"
+    tu.write_text("#include <petsc.h>\n#include <petscdmda.h>\n#include <petscksp.h>\n#include <parmgmc/mc_sor.h>\nvoid *calls_[] = {\n" + "".join(f"  (void *)&{c},\n" for c in calls["mcsor"] + calls["petsc"]) + "};\n")
+    for idx in ([], ["-DPETSC_DECL_MOCK_64BIT_INDICES"]):
+        r = subprocess.run([GCC, "-std=gnu11", "-fsyntax-only", "-Wall", "-Wextra", "-Werror", *idx, "-I", str(ROOT / "tests" / "petsc_decl_mock"), str(tu)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr
 
 
 def test_adapter_calls_only_exported_c_abi_functions():

@@ -114,3 +114,86 @@ def test_two_ranks_sharing_the_gpu_print_the_self_describing_record():
     assert [x["rank"] for x in rk] == [0, 1] and all(x["transport"] == "ipc" and x["device"] == 0 and len(x["pci_bus_id"]) >= 7 for x in rk)
     assert rk[0]["neighbour_ranks"] == [-1, 1] and rk[1]["neighbour_ranks"] == [0, -1]
     assert rk[0]["peer_access_lo_hi"] == [-1, 1] and rk[1]["peer_access_lo_hi"] == [1, -1]
+
+
+def _oracle_chain(n: int, steps: int):
+    """the chain bench.py times: b = 1, x0 = 0, kappa = 10, omega = 1, `steps` forward red-black Gibbs sweeps, noise
+    counters 0..steps-1 of seed 0xCAFE"""
+    import numpy as np
+
+    import oracle as O
+
+    A = O.shifted_laplace(n, n, n, 10.0)
+    return O.gibbs_samples(A, O.coloring_redblack(n, n, n), np.ones(A.n), np.zeros(A.n), steps, lambda d: O.noise_grid(n, n, n, 0xCAFE, d), 1.0, O.SOR_FORWARD, True)
+
+
+def test_dump_outputs_writes_the_whole_sample_or_a_fixed_seeded_part(tmp_path, monkeypatch):
+    """bench.dump_outputs without a GPU (one rank, the grid's from_cvec stood in by the identity): below DUMP_FULL_MAX
+    unknowns every entry, above it DUMP_SAMPLE entries at positions that do not change from run to run; f64, <= 64 MB"""
+    import numpy as np
+    import torch
+
+    monkeypatch.syspath_prepend(str(ROOT))
+    monkeypatch.setenv("HSA_ENABLE_IPC_MODE_LEGACY", os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))  # bench sets it on import
+    import bench
+
+    class Identity:
+        def __init__(self, n):
+            self.n = n
+
+        def from_cvec(self, y):
+            return y
+
+    for n in (24, 170):
+        total = n ** 3
+        y = torch.arange(total, dtype=torch.float64) * 0.5
+        shapes = [bench.dump_outputs(str(tmp_path / f"{n}_{k}"), Identity(total), y, n, 0, 1) for k in (0, 1)]
+        assert shapes[0] == shapes[1]
+        files = [sorted((tmp_path / f"{n}_{k}").glob("*.npy")) for k in (0, 1)]
+        assert sum(f.stat().st_size for f in files[0]) <= 64 << 20
+        for a, b in zip(*files):
+            assert a.name == b.name and np.array_equal(np.load(a), np.load(b))
+        if total <= bench.DUMP_FULL_MAX:
+            assert shapes[0] == {"y": [total]}
+            v = np.load(tmp_path / f"{n}_0" / "y.npy")
+            assert v.dtype == np.float64 and np.array_equal(v, y.numpy())
+        else:
+            assert shapes[0] == {"y_sample": [bench.DUMP_SAMPLE], "y_sample_index": [bench.DUMP_SAMPLE]}
+            v = np.load(tmp_path / f"{n}_0" / "y_sample.npy")
+            i = np.load(tmp_path / f"{n}_0" / "y_sample_index.npy")
+            assert v.dtype == np.float64 and i.dtype == np.float64 and np.all(np.diff(i) > 0) and i[-1] < total
+            assert np.array_equal(v, 0.5 * i)
+
+
+@pytest.mark.gpu
+def test_dump_outputs_hold_the_timed_chain(tmp_path):
+    """--dump-outputs: the sample after the last of --steps timed steps, which run the chain from x0 = 0 with noise
+    counters 0..steps-1 whatever the warm-up and the adaptive settle phase did -- the CPU oracle's chain"""
+    import numpy as np
+
+    n, steps = 64, 3
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--grid-n", str(n), "--steps", str(steps), "--warmup", "2", "--no-mgmc", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["steps"] == steps and d["ms_per_step"] > 0 and d["dump_outputs"]["arrays"] == {"y": [n ** 3]}
+    got = np.load(tmp_path / "y.npy")
+    want = _oracle_chain(n, steps)
+    assert got.dtype == np.float64 and np.abs(got - want).max() / np.abs(want).max() < 1e-13
+
+
+@pytest.mark.gpu
+def test_two_ranks_dump_the_same_chain_as_the_oracle(tmp_path):
+    """--dump-outputs on the one-GPU rehearsal of `bench.py --gpus 2`: rank 0 writes both z-slabs in natural order"""
+    import numpy as np
+
+    n, steps = 64, 4
+    env = dict(os.environ, PMG_BENCH_SHARE_DEVICE="1", PMG_BENCH_SPAWN_TIMEOUT="500")
+    env.pop("WORLD_SIZE", None)
+    env.pop("RANK", None)
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--grid-n", str(n), "--steps", str(steps), "--warmup", "2", "--no-mgmc", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert d["n_gpus"] == 2 and d["steps"] == steps and d["halo_check"].startswith("bit-identical")
+    got = np.load(tmp_path / "y.npy")
+    want = _oracle_chain(n, steps)
+    assert np.abs(got - want).max() / np.abs(want).max() < 1e-13
