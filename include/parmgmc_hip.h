@@ -123,6 +123,19 @@ pmg_status pmg_mcsor_from_layout(pmg_mcsor mc, const double *lay_dev, double *na
 pmg_status pmg_mcsor_apply_layout(pmg_mcsor mc, const double *b_lay, double *y_lay, void *stream);
 pmg_status pmg_mcsor_sample_layout(pmg_mcsor mc, const double *b_lay, double *y_lay, int32_t its, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, void *stream);
 pmg_status pmg_mcsor_residual_layout(pmg_mcsor mc, const double *b_lay, const double *y_lay, double *r_lay, void *stream);
+/* MANY INDEPENDENT CHAINS of one operator per call (examples/ex6.c:131-183 runs 1000 chains x 200 samples for the
+   covariance-error study, examples/ex7.c:113-192 eight chains for R-hat): one launch per colour advances all of them.
+   Y is n x nchains doubles on the device, row-major with the chain index fastest (Y[row * nchains + c], a contiguous (n, C)
+   float64 torch tensor), natural row numbering; b is ONE natural-order vector of n entries shared by all chains.  Chain c
+   draws with key seeds_host[c] and the counters of the single-chain call, so column c after the call equals, bit for bit,
+   pmg_mcsor_apply / pmg_mcsor_sample on that column alone with seed = seeds_host[c]; *counter_out is the single-chain value.
+   Per-chain workspace is allocated on first use, grows with nchains and lives until pmg_mcsor_destroy.
+   PMG_ERR_ARG_OUTOFRANGE: nchains < 1 or sizes beyond 64-bit / launch limits; PMG_ERR_ARG_NULL: NULL seeds, b or Y;
+   PMG_ERR_ARG_WRONGSTATE: not set up (these checks run before any device work); PMG_ERR_SUP: a low-rank (MATLRC) update. */
+/* deterministic MCSORApply (src/mc_sor.c:216-239) on C chains */
+pmg_status pmg_mcsor_apply_chains(pmg_mcsor mc, int32_t nchains, const double *b_dev, double *Y_dev, void *stream);
+/* pmg_mcsor_sample (src/pc_mcgibbs.c:155-188, src/pc_sorgibbs.c:76-103) on C chains */
+pmg_status pmg_mcsor_sample_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds_host, const double *b_dev, double *Y_dev, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream);
 /* Building blocks of the ROW-BLOCK distributed sampler (MCSORApply_MPIAIJ, src/mc_sor.c:298-381: for every colour,
    update the ghost values, then sweep the colour's rows): a rank holds its rows with the off-process columns appended
    as ghost rows (identity rows in an extra, never swept colour); the caller moves ghost values between the per-colour
@@ -414,6 +427,17 @@ pmg_status pmg_mgmc_sample(pmg_mgmc mg, const double *b_nat_dev, double *y_nat_d
    low-rank steps, listed at the definition (pmg_mgmc.c) and in DESIGN.md section 6.  per_level_host: nlevels doubles or NULL.
    What bench.py divides by the measured time per sample for the roofline fraction of its V-cycle lines. */
 pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc mg, double *total, double *per_level_host);
+/* pmg_mgmc_sample on C chains (examples/ex6.c:131-183, examples/ex7.c:113-192: many chains of one target), for hierarchies
+   from pmg_mgmc_create_hierarchy on one device whose levels are all sliced-ELL, with either coarse sampler and either
+   correction form.  Layout, seeds, counters and bit identity as for pmg_mcsor_sample_chains: chain c uses seeds_host[c] and
+   per level level_seed(seeds_host[c], l), sample s the counters [64 s, 64 s + 64).  The callback follows
+   pmg_sample_callback's rules with all chains' samples (Y_nat_dev, n x nchains, chain fastest).  PMG_ERR_SUP: DMDA
+   hierarchies (pmg_mgmc_create_dmda*), row-block hierarchies, a low-rank update; other errors as pmg_mcsor_sample_chains. */
+typedef int (*pmg_chains_callback)(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
+pmg_status pmg_mgmc_sample_chains(pmg_mgmc mg, int32_t nchains, const uint64_t *seeds_host, const double *b_nat_dev, double *Y_nat_dev, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
+/* algorithmic bytes of ONE V-cycle advancing all C chains (the chains analogue of pmg_mgmc_get_algorithmic_bytes): shared
+   operands (matrices, idiag, sqrtdiag, the shared b, P, W) counted once, iterates and per-chain right-hand sides C times */
+pmg_status pmg_mgmc_get_algorithmic_bytes_chains(pmg_mgmc mg, int32_t nchains, double *total, double *per_level_host);
 /* Diagnostics: ONE kernel of the V-cycle on caller-supplied device vectors in the level's own layout (single device).
    They exist for the parity tests at 257^3 / 513^3, where a whole oracle cycle is out of reach: the tests run one
    kernel and compare sampled rows with the oracle's row arithmetic (PCMG pieces entered at reference

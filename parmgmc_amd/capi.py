@@ -265,6 +265,10 @@ _sig = {
     "pmg_woodbury_correct": (_int, [_vp, _vp, _vp]),
     "pmg_woodbury_get_correction": (_int, [_vp, _vp]),
     "pmg_woodbury_destroy": (_int, [C.POINTER(_vp)]),
+    "pmg_mcsor_apply_chains": (_int, [_vp, _i32, _vp, _vp, _vp]),
+    "pmg_mcsor_sample_chains": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp]),
+    "pmg_mgmc_sample_chains": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
+    "pmg_mgmc_get_algorithmic_bytes_chains": (_int, [_vp, _i32, C.POINTER(_dbl), _vp]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)
@@ -336,6 +340,7 @@ DELETER = C.CFUNCTYPE(C.c_int, C.c_void_p)
 SHELL_APPLY = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 PC_CTOR = C.CFUNCTYPE(C.c_int, C.c_void_p)
 SAMPLE_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p)
+CHAINS_CALLBACK = C.CFUNCTYPE(C.c_int, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p)
 
 
 def check(status: int) -> None:

@@ -122,6 +122,16 @@ pmg_status pmg_chol_sample(pmg_chol ch, const double *b_dev, double *y_dev, int 
   return PMG_SUCCESS;
 }
 
+/* pmg_chol_sample(noisy) on C right-hand sides B (n x C, chain fastest): column c is the single-chain sample with seed
+   keys[c] -- its noise is fill_normal_rows's stream for that key, the two triangular products keep tri_gemv's sums */
+pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *B, double *Y, double *Xi, double *V, void *stream)
+{
+  PMG_KERNEL(pmgk_fill_normal_rows_chains(ch->n, nchains, keys_dev, counter, Xi, stream));
+  PMG_KERNEL(pmgk_tri_gemv_chains(ch->n, 0, ch->W_lo, nchains, B, Xi, V, stream)); /* V = L^-1 B + Xi */
+  PMG_KERNEL(pmgk_tri_gemv_chains(ch->n, 1, ch->W_up, nchains, V, NULL, Y, stream)); /* Y = L^-T V */
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_chol_destroy(pmg_chol *ch)
 {
   if (!ch || !*ch) return PMG_SUCCESS;

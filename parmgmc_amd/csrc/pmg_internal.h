@@ -88,6 +88,23 @@ pmg_status pmg_dev_upload(void **p, const void *host, size_t bytes);
 void       pmg_dev_free(void *p);
 
 
+/* multi-chain entry points (pmg_mcsor.c): a device copy of C noise keys, uploaded only when they change */
+typedef struct {
+  uint64_t *dev, *host;
+  int64_t   cap, n;
+} pmg_keybuf;
+pmg_status pmg_keybuf_set(pmg_keybuf *k, const uint64_t *keys, int64_t n, void *stream);
+void       pmg_keybuf_free(pmg_keybuf *k);
+/* ld rows of nchains chains: PMG_ERR_ARG_OUTOFRANGE when the element count or the chain count exceeds what the launches index */
+pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains);
+/* building blocks of the chains V-cycle on layout vectors (n x C, chain fastest; bcs = chain stride of b: 0 shared, 1 per chain) */
+pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *Y_lay, void *stream);
+pmg_status pmg_mcsor_residual_chains(pmg_mcsor mc, int32_t nchains, const double *b_lay, int bcs, const double *Y_lay, double *R_lay, void *stream);
+pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc); /* PMG_ERR_SUP for what the chains kernels do not carry */
+const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc);      /* layout -> natural row map on the device (-1 in pad rows) */
+/* pmg_chol.c: the exact sample y = L^-T (L^-1 b + xi) on C right-hand sides; Xi, V: n x C work arrays */
+pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *B, double *Y, double *Xi, double *V, void *stream);
+
 /* pmg_rowblock.c */
 void pmg_mcsor_adopt_arrays(pmg_mcsor mc, int32_t *rowptr, int32_t *colidx, double *vals);
 

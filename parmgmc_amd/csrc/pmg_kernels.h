@@ -188,6 +188,17 @@ int pmgk_fill_normal_rows(int64_t n, uint64_t seed, uint64_t sweep, double *xi, 
 int pmgk_fill_normal_batch(int nstreams, int64_t n, const uint64_t *seed, const uint64_t *sweep, const double *scale, double *xi, int64_t stride, void *stream); /* host arrays of seeds / sweeps */
 int pmgk_fill_normal_rows_scaled(int64_t n, uint64_t seed, uint64_t sweep, const double *scale, double *xi, void *stream); /* xi = scale o z */
 
+/* many chains of one operator per launch (kernels_chains.hip).  A multi-chain vector is n x C doubles, chain fastest:
+   (row, chain) at row * C + chain.  Right-hand sides take a chain stride bcs: 0 = one vector shared by all chains, 1 = one per
+   chain.  keys: device array of the C chains' noise keys.  Column c of every result equals the single-chain kernel's. */
+int pmgk_sell_color_sweep_chains(const pmgk_sell *S, int slice0, int nsl, double omega, int noisy, const uint64_t *keys, uint64_t sweep, int32_t nchains, const double *b, int bcs, double *Y, void *stream);
+int pmgk_sell_residual_chains(const pmgk_sell *S, int32_t nchains, const double *b, int bcs, const double *Y, double *R, void *stream);
+int pmgk_permute_in_chains(int32_t ld, const int32_t *orig, int32_t nchains, const double *nat, int bcs, double *perm, void *stream);
+int pmgk_permute_out_chains(int32_t ld, const int32_t *orig, int32_t nchains, const double *perm, double *nat, void *stream);
+int pmgk_csr_spmv_rows_chains(int32_t nrows, const int32_t *rowpos, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t nchains, const double *X, double *Y, int accumulate, double *zero, void *stream);
+int pmgk_fill_normal_rows_chains(int64_t n, int32_t nchains, const uint64_t *keys, uint64_t sweep, double *Xi, void *stream);
+int pmgk_tri_gemv_chains(int32_t n, int upper, const double *M, int32_t nchains, const double *X, const double *Add, double *Out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -37,6 +37,11 @@ struct pmg_mcsor_s {
   double  *b_p, *y_p, *r_p; /* permuted scratch vectors */
   pmg_lrc  lrc;             /* MATLRC: rank-k update B S B^T (src/mc_sor.c:572-595) */
   int64_t  noise_row0;      /* global row of local row 0 (row block of a distributed matrix) */
+  /* multi-chain workspace (pmg_mcsor_*_chains): allocated on first use, grows with the chain count */
+  int32_t    ch_cap;  /* chains ch_Y holds */
+  double    *ch_b;    /* [ld] the shared right-hand side in the layout */
+  double    *ch_Y;    /* [ld * ch_cap] the chains in the layout, chain fastest */
+  pmg_keybuf ch_keys; /* the chains' noise keys */
 };
 
 /* --- colouring rules -------------------------------------------------------------------------------- */
@@ -250,8 +255,18 @@ pmg_status pmg_mcsor_set_coloring(pmg_mcsor mc, int rule, const int32_t *user_co
   return PMG_SUCCESS;
 }
 
+static void mcsor_free_chains(pmg_mcsor mc)
+{
+  pmg_dev_free(mc->ch_b);
+  pmg_dev_free(mc->ch_Y);
+  pmg_keybuf_free(&mc->ch_keys);
+  mc->ch_b = mc->ch_Y = NULL;
+  mc->ch_cap          = 0;
+}
+
 static void mcsor_free_setup(pmg_mcsor mc)
 {
+  mcsor_free_chains(mc);
   free(mc->colors);
   free(mc->cslice);
   free(mc->orig_host);
@@ -713,6 +728,141 @@ pmg_status pmg_mcsor_set_lowrank(pmg_mcsor mc, int32_t k, const double *B_host, 
   pmg_status st = pmg_lrc_build(&mc->lrc, k, mc->S.ld, mc->n, B_host, pos, S_host, mcsor_det_sweep, mc);
   free(pos);
   return st;
+}
+
+/* ---- many chains per launch (pmg_mcsor_apply_chains / pmg_mcsor_sample_chains) --------------------------------------
+   The iterate of C chains lives in the layout as ld x C doubles, chain fastest; one launch per colour sweeps every chain
+   (kernels_chains.hip).  Column c follows exactly the single-chain path: same colour order, same counters, key seeds[c]. */
+
+pmg_status pmg_keybuf_set(pmg_keybuf *k, const uint64_t *keys, int64_t n, void *stream)
+{
+  if (k->n == n && n > 0 && !memcmp(k->host, keys, sizeof(uint64_t) * (size_t)n)) return PMG_SUCCESS;
+  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* launches in flight may still read the keys; the host copy is the source of the last upload */
+  if (n > k->cap) {
+    pmg_keybuf_free(k);
+    k->host = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n);
+    PMG_CHECK(k->host, PMG_ERR_MEM, "out of host memory");
+    PMG_CALL(pmg_dev_alloc((void **)&k->dev, sizeof(uint64_t) * (size_t)n));
+    k->cap = n;
+  }
+  memcpy(k->host, keys, sizeof(uint64_t) * (size_t)n);
+  k->n = n;
+  PMG_HIP(hipMemcpyAsync(k->dev, k->host, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, (hipStream_t)stream));
+  return PMG_SUCCESS;
+}
+
+void pmg_keybuf_free(pmg_keybuf *k)
+{
+  pmg_dev_free(k->dev);
+  free(k->host);
+  memset(k, 0, sizeof *k);
+}
+
+/* the launches index ld x C elements with 64-bit offsets; grids of 256-thread blocks over them and chunks of 64 chains in
+   blockIdx.y must stay inside the launch limits */
+pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains)
+{
+  PMG_CHECK(nchains >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", nchains);
+  PMG_CHECK(nchains <= 64 * 65535, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d exceeds %d", nchains, 64 * 65535);
+  PMG_CHECK(ld <= ((int64_t)1 << 40) / nchains, PMG_ERR_ARG_OUTOFRANGE, "%lld rows x %d chains exceed 2^40 elements", (long long)ld, nchains);
+  return PMG_SUCCESS;
+}
+
+pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc)
+{
+  PMG_CHECK(!mc->lrc, PMG_ERR_SUP, "multi-chain sampling of an operator with a low-rank (MATLRC) update is not supported");
+  return PMG_SUCCESS;
+}
+
+const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc) { return mc->S.orig; }
+
+/* `its` times the directional sweeps of the sweep type (symmetric = forward + backward), every directional sweep with the next
+   counter when noisy: pmg_mcsor_sample_layout / pmg_mcsor_apply_layout on C chains */
+pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *Y_lay, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  pmgk_sell S = mc->S;
+  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
+  uint64_t ctr = counter0;
+  for (int32_t it = 0; it < its; ++it) {
+    const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+    for (int d = 0; d < ndir; ++d) {
+      const int      dir   = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
+      const uint64_t sweep = noisy ? ctr++ : 0;
+      int            rc    = 0;
+      pmg_trace_begin(PMG_EVENT_MULTICOL_SOR);
+      if (dir == PMG_SOR_FORWARD_SWEEP) {
+        for (int32_t c = 0; c < mc->ncolors && !rc; ++c) rc = pmgk_sell_color_sweep_chains(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
+      } else {
+        for (int32_t c = mc->ncolors - 1; c >= 0 && !rc; --c) rc = pmgk_sell_color_sweep_chains(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
+      }
+      pmg_trace_end();
+      PMG_KERNEL(rc);
+    }
+  }
+  if (counter_out) *counter_out = ctr;
+  return PMG_SUCCESS;
+}
+
+pmg_status pmg_mcsor_residual_chains(pmg_mcsor mc, int32_t nchains, const double *b_lay, int bcs, const double *Y_lay, double *R_lay, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  PMG_KERNEL(pmgk_sell_residual_chains(&mc->S, nchains, b_lay, bcs, Y_lay, R_lay, stream));
+  return PMG_SUCCESS;
+}
+
+static pmg_status mcsor_chains_workspace(pmg_mcsor mc, int32_t nchains, void *stream)
+{
+  if (!mc->ch_b) PMG_CALL(pmg_dev_alloc((void **)&mc->ch_b, sizeof(double) * (size_t)mc->S.ld));
+  if (nchains > mc->ch_cap) {
+    PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
+    pmg_dev_free(mc->ch_Y);
+    mc->ch_Y   = NULL;
+    mc->ch_cap = 0;
+    PMG_CALL(pmg_dev_alloc((void **)&mc->ch_Y, sizeof(double) * (size_t)mc->S.ld * (size_t)nchains));
+    mc->ch_cap = nchains;
+  }
+  return PMG_SUCCESS;
+}
+
+/* argument checks of both entry points, before any device work */
+static pmg_status mcsor_chains_args(pmg_mcsor mc, int32_t nchains, int need_seeds, const uint64_t *seeds, const double *b, const double *Y)
+{
+  PMG_CHECK(mc, PMG_ERR_ARG_NULL, "null MCSOR");
+  PMG_CHECK(nchains >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", nchains);
+  PMG_CHECK(b && Y && (seeds || !need_seeds), PMG_ERR_ARG_NULL, "null argument");
+  PMG_CALL(pmg_mcsor_chains_supported(mc));
+  PMG_CHECK(mc->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_mcsor_setup first");
+  return pmg_chains_size_check(mc->S.ld, nchains);
+}
+
+/* the deterministic sweep of the current type on every chain (pmg_mcsor_apply per column) */
+pmg_status pmg_mcsor_apply_chains(pmg_mcsor mc, int32_t nchains, const double *b, double *Y, void *stream)
+{
+  PMG_CALL(mcsor_chains_args(mc, nchains, 0, NULL, b, Y));
+  PMG_CALL(mcsor_ready(mc));
+  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
+  PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->ch_b, stream));
+  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
+  PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, NULL, 0, 0, 1, 0, NULL, mc->ch_b, 0, mc->ch_Y, stream));
+  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
+  return PMG_SUCCESS;
+}
+
+/* pmg_mcsor_sample per column: chain c with seed seeds[c], draw d of the call with counter counter0 + d */
+pmg_status pmg_mcsor_sample_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds, const double *b, double *Y, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream)
+{
+  PMG_CALL(mcsor_chains_args(mc, nchains, 1, seeds, b, Y));
+  PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
+  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CALL(mcsor_ready(mc));
+  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
+  PMG_CALL(pmg_keybuf_set(&mc->ch_keys, seeds, nchains, stream));
+  PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->ch_b, stream));
+  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
+  PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, mc->ch_keys.dev, 1, scaled, its, counter0, counter_out, mc->ch_b, 0, mc->ch_Y, stream));
+  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
+  return PMG_SUCCESS;
 }
 
 /* the CSR arrays pmg_mcsor_create_csr borrowed become the object's (malloc'd by the caller, freed with the object) */

@@ -25,6 +25,18 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr())
 
 
+def _chains(Y, n):
+    """(pointer, C) of a contiguous (n, C) float64 CUDA tensor: the chains layout of the C-ABI, chain fastest"""
+    assert Y.dim() == 2 and Y.shape[0] == n, f"need an (n, C) tensor with n = {n}"
+    return _ptr(Y), int(Y.shape[1])
+
+
+def _seeds(seeds, nchains):
+    s = np.ascontiguousarray([int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds], np.uint64)
+    assert len(s) == nchains, f"{len(s)} seeds for {nchains} chains"
+    return s
+
+
 class MCSOR:
     """MCSOR on an assembled AIJ matrix (reference include/parmgmc/mc_sor.h:21-30)."""
 
@@ -85,6 +97,20 @@ class MCSOR:
 
     def residual(self, b, y, r):
         check(lib.pmg_mcsor_residual(self._h, _ptr(b), _ptr(y), _ptr(r), _stream()))
+
+    # --- many chains per call: Y is a contiguous (n, C) float64 tensor, b one vector shared by all chains ---
+    def apply_chains(self, b, Y):
+        """the deterministic sweep on every column of Y (= apply per column)"""
+        p, nc = _chains(Y, self.n)
+        check(lib.pmg_mcsor_apply_chains(self._h, nc, _ptr(b), p, _stream()))
+
+    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, scaled: bool = True) -> int:
+        """`its` samples of C chains; column c equals sample(b, Y[:, c], its, seeds[c], counter0, scaled) bit for bit"""
+        p, nc = _chains(Y, self.n)
+        s = _seeds(seeds, nc)
+        out = C.c_uint64()
+        check(lib.pmg_mcsor_sample_chains(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(scaled), counter0, C.byref(out), _stream()))
+        return out.value
 
     # --- storage layout and per-colour sweeps (building blocks of the row-block distributed sampler) ---
     def layout_len(self) -> int:
@@ -414,6 +440,37 @@ class MGMC:
             cb = capi.SAMPLE_CALLBACK(_cb)
         check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, None, _stream()))
         return out.value
+
+    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None) -> int:
+        """`its` samples of C chains on a hierarchy from from_hierarchy: Y is a contiguous (n, C) float64 tensor, b one vector
+        shared by all chains; column c equals sample(b, Y[:, c], its, seeds[c], ...) bit for bit.  callback(it, Y) after
+        every sample; a raised exception aborts the loop."""
+        p, nc = _chains(Y, self.n)
+        s = _seeds(seeds, nc)
+        out = C.c_uint64()
+        cb = None
+        if callback is not None:
+
+            def _cb(it, ptr, n, nchains, _ctx):
+                try:
+                    callback(it, Y)
+                    return 0
+                except Exception:  # pragma: no cover
+                    import traceback
+
+                    traceback.print_exc()
+                    return 77
+
+            cb = capi.CHAINS_CALLBACK(_cb)
+        check(lib.pmg_mgmc_sample_chains(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(guesszero), counter0, C.byref(out), cb, None, _stream()))
+        return out.value
+
+    def algorithmic_bytes_chains(self, nchains: int):
+        """(total, per_level): algorithmic bytes of one V-cycle advancing `nchains` chains (pmg_mgmc_get_algorithmic_bytes_chains)"""
+        tot = C.c_double()
+        per = np.zeros(self.levels)
+        check(lib.pmg_mgmc_get_algorithmic_bytes_chains(self._h, nchains, C.byref(tot), per.ctypes.data))
+        return tot.value, per
 
     def destroy(self):
         if self._h:
