@@ -168,7 +168,9 @@ MG_DEFAULT = dict(scaled=False, omega=1.0, sweep=1, nu=1, coarse="cholsampler", 
     ((9, 9, 33), 4, 5, {"env": {"PMG_MG_REPLICATE_BELOW": "50"}, "scaled": True, "sweep": 3}),  # three distributed levels; on the 9-plane level the ranks own 2,2,2,1,2 planes (5 ranks + this process = the box's limit of 6 GPU processes)
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400"}, "lowrank": True, "scaled": True, "sweep": 3}),  # config 5 across ranks: low-rank update on distributed and replicated levels
     ((17, 17, 17), 3, 2, {"lowrank": True, "literal": True, "coarse": "gibbs", "coarse_its": 2, "scaled": True}),
-], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks"])
+    ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_ST27_PAIR_SLAB": "0"}, "sweep": 2}),  # one launch per colour on the distributed class-stencil levels
+    ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_GRID_FUSED_RR_SLAB": "0"}, "sweep": 3}),  # residual and restriction of the grid slabs as two kernels
+], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks", "st27_pair_slab_0_3ranks", "fused_rr_slab_0_3ranks"])
 def test_distributed_vcycle_reproduces_the_single_device_chain(grid, levels, world, opts):
     """z-slab MGMC (pmg_mgmc_create_dmda_slab) with `world` ranks sharing the one GPU over the ipc transport: sweeps
     with per-phase halos, residual halo + restriction, all-gather into the replicated coarse part, prolongation onto

@@ -84,8 +84,12 @@ def test_chol_sampler_matches_oracle():
     assert e.value.code == 81 and "leading minor of order 2" in str(e.value)
 
 
-def oracle_chain(grid, kappa, levels, b, y0, its, seed, counter0, guesszero, nu=1, scaled=False, omega=1.0, sweep=O.SOR_FORWARD, coarse="cholsampler", coarse_its=1):
-    lv = oracle_hierarchy(*grid, kappa, levels)
+def oracle_chain(grid, kappa, levels, b, y0, its, seed, counter0, guesszero, nu=1, scaled=False, omega=1.0, sweep=O.SOR_FORWARD, coarse="cholsampler", coarse_its=1, lv=None, shift=None):
+    """`lv`: a hierarchy from oracle_hierarchy(grid, kappa, levels) to reuse; `shift`: {level: k} moves that level's noise
+    counters by k draws (a negative control: the chain must then differ from the sampler's)"""
+    if lv is None:
+        lv = oracle_hierarchy(*grid, kappa, levels)
+    shift = shift or {}
     top = levels - 1
     csr = [O.CSR.from_scipy(x["A"]) for x in lv]
     cols = [O.coloring_parity8(*x["dims"]) for x in lv]
@@ -95,7 +99,7 @@ def oracle_chain(grid, kappa, levels, b, y0, its, seed, counter0, guesszero, nu=
     out = []
     for it in range(its):
         s = counter0 + it
-        ctr = {l: 64 * s for l in range(levels)}
+        ctr = {l: 64 * s + shift.get(l, 0) for l in range(levels)}
 
         def noise(l):
             c = ctr[l]

@@ -72,11 +72,12 @@ def _init(rank, world, port):
     dist.init_process_group("gloo", rank=rank, world_size=world)
 
 
-def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury):
+def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury, env=None):
     import torch
     import torch.distributed as dist
 
     try:
+        os.environ.update(env or {})  # runtime switches: read at their first use, after this
         _init(rank, world, port)
         from parmgmc_amd.dist import CRowBlock
         from parmgmc_amd.wrappers import WoodburySampler
@@ -119,14 +120,15 @@ def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,sweep_type", [(2, 1), (3, 3)], ids=["2ranks", "3ranks_symmetric"])
-def test_c_row_block_sampler_is_the_single_device_chain(world, sweep_type):
+@pytest.mark.parametrize("world,sweep_type,env", [(2, 1, {}), (3, 3, {}), (3, 2, {"PMG_DISTMCSOR_REFRESH_BY_COLOUR": "1"})], ids=["2ranks", "3ranks_symmetric", "3ranks_backward_refresh_by_colour"])
+def test_c_row_block_sampler_is_the_single_device_chain(world, sweep_type, env):
+    """env: PMG_DISTMCSOR_REFRESH_BY_COLOUR=1 refreshes the ghost rows colour by colour instead of in one all-gather"""
     import torch
 
     from parmgmc_amd import MCSOR
 
     omega, its = 1.15, 3
-    parts = _run(_sampler_worker, world, omega, sweep_type, its, False)
+    parts = _run(_sampler_worker, world, omega, sweep_type, its, False, env)
     A = lshape(1)
     rng = np.random.default_rng(5)
     b_all, y_all = rng.standard_normal(A.shape[0]), rng.standard_normal(A.shape[0])
