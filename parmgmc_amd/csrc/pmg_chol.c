@@ -43,7 +43,8 @@ pmg_status pmg_chol_create_csr_lowrank(int32_t n, const int32_t *rowptr, const i
   *out = NULL;
   PMG_CHECK(n >= 1, PMG_ERR_ARG_OUTOFRANGE, "n = %d", n);
   PMG_CHECK(rowptr && colidx && vals, PMG_ERR_ARG_NULL, "null CSR array");
-  PMG_CHECK(k >= 0 && (k == 0 || (B_host && S_host)), PMG_ERR_ARG_NULL, "low-rank factors missing (k = %d)", k);
+  PMG_CHECK(k >= 0 && k <= 64, PMG_ERR_ARG_OUTOFRANGE, "rank k = %d (0..64 supported)", k);
+  PMG_CHECK(k == 0 || (B_host && S_host), PMG_ERR_ARG_NULL, "low-rank factors missing (k = %d)", k);
   const int32_t npad = (n + 31) / 32 * 32;
   PMG_CHECK((double)npad * npad * 8 * 4 < 96e9, PMG_ERR_SUP, "dense coarse sampler limited to a few tens of thousands of rows (n = %d); coarsen further", n);
   const size_t nn = (size_t)npad * npad;

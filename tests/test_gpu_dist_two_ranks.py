@@ -128,7 +128,7 @@ def _mg_worker(rank, world, port, grid, kappa, levels, opts, its, q, transport):
     mg.set_correction_form(opts["literal"])
     lo, hi = mg.plane_range[0] * nx * ny, mg.plane_range[1] * nx * ny
     if opts.get("lowrank"):
-        B, S = _ball_factors(grid)
+        B, S = _ball_factors(grid, opts.get("lowrank_k", 3))
         mg.set_lowrank(B[lo:hi], S)  # this rank's rows of the observation vectors
     mg.setup()
     rng = np.random.default_rng(5)
@@ -145,16 +145,22 @@ def _mg_worker(rank, world, port, grid, kappa, levels, opts, its, q, transport):
     dist.destroy_process_group()
 
 
-def _ball_factors(grid):
-    """three ball-indicator observation vectors (reference src/obs.c:39-50) straddling the slab faces"""
+def _ball_factors(grid, k=3):
+    """three ball-indicator observation vectors (reference src/obs.c:39-50) straddling the slab faces; k > 3: k smaller
+    balls at random centres (the rank range's top: k = 64)"""
     nx, ny, nz = grid
     X, Y, Z = np.meshgrid(np.linspace(0, 1, nx), np.linspace(0, 1, ny), np.linspace(0, 1, nz), indexing="ij")
     pts = np.stack([X.ravel(order="F"), Y.ravel(order="F"), Z.ravel(order="F")], 1)
-    B = np.zeros((nx * ny * nz, 3))
-    for c, (ctr, r) in enumerate([((0.3, 0.4, 0.5), 0.22), ((0.7, 0.6, 0.25), 0.2), ((0.5, 0.3, 0.8), 0.18)]):
+    balls = [((0.3, 0.4, 0.5), 0.22), ((0.7, 0.6, 0.25), 0.2), ((0.5, 0.3, 0.8), 0.18)]
+    if k != 3:
+        rng = np.random.default_rng(k)
+        balls = [(tuple(rng.uniform(0.15, 0.85, 3)), rng.uniform(0.1, 0.14)) for _ in range(k)]
+    B = np.zeros((nx * ny * nz, k))
+    for c, (ctr, r) in enumerate(balls):
         inside = ((pts - np.asarray(ctr)) ** 2).sum(1) < r * r
         B[inside, c] = 1.0 / inside.sum()
-    return B, np.array([40.0, 90.0, 60.0])
+    assert (B.sum(0) > 0).all()
+    return (B, np.array([40.0, 90.0, 60.0])) if k == 3 else (B, np.random.default_rng(k + 1).uniform(20.0, 90.0, k))
 
 
 MG_DEFAULT = dict(scaled=False, omega=1.0, sweep=1, nu=1, coarse="cholsampler", coarse_its=1, literal=False, env={})
@@ -168,9 +174,10 @@ MG_DEFAULT = dict(scaled=False, omega=1.0, sweep=1, nu=1, coarse="cholsampler", 
     ((9, 9, 33), 4, 5, {"env": {"PMG_MG_REPLICATE_BELOW": "50"}, "scaled": True, "sweep": 3}),  # three distributed levels; on the 9-plane level the ranks own 2,2,2,1,2 planes (5 ranks + this process = the box's limit of 6 GPU processes)
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400"}, "lowrank": True, "scaled": True, "sweep": 3}),  # config 5 across ranks: low-rank update on distributed and replicated levels
     ((17, 17, 17), 3, 2, {"lowrank": True, "literal": True, "coarse": "gibbs", "coarse_its": 2, "scaled": True}),
+    ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400"}, "lowrank": True, "lowrank_k": 64, "scaled": True, "sweep": 3}),  # the top of the rank range
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_ST27_PAIR_SLAB": "0"}, "sweep": 2}),  # one launch per colour on the distributed class-stencil levels
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_GRID_FUSED_RR_SLAB": "0"}, "sweep": 3}),  # residual and restriction of the grid slabs as two kernels
-], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks", "st27_pair_slab_0_3ranks", "fused_rr_slab_0_3ranks"])
+], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks", "lowrank_k64_3ranks", "st27_pair_slab_0_3ranks", "fused_rr_slab_0_3ranks"])
 def test_distributed_vcycle_reproduces_the_single_device_chain(grid, levels, world, opts):
     """z-slab MGMC (pmg_mgmc_create_dmda_slab) with `world` ranks sharing the one GPU over the ipc transport: sweeps
     with per-phase halos, residual halo + restriction, all-gather into the replicated coarse part, prolongation onto
@@ -200,7 +207,7 @@ def test_distributed_vcycle_reproduces_the_single_device_chain(grid, levels, wor
     one.set_coarse(o["coarse"], o["coarse_its"])
     one.set_correction_form(o["literal"])
     if o.get("lowrank"):
-        one.set_lowrank(*_ball_factors(grid))
+        one.set_lowrank(*_ball_factors(grid, o.get("lowrank_k", 3)))
     one.setup()
     yd = torch.as_tensor(y_all, device="cuda")
     want = []
@@ -215,17 +222,21 @@ def test_distributed_vcycle_reproduces_the_single_device_chain(grid, levels, wor
     assert np.array_equal(np.concatenate([x[1] for x in parts]), yd.cpu().numpy())
 
 
-def _csr_lowrank_factors(n):
-    """three observation-like vectors with supports that straddle every row-block cut, and their precisions"""
+def _csr_lowrank_factors(n, k=3):
+    """three observation-like vectors with supports that straddle every row-block cut, and their precisions; k > 3: k
+    narrower ones spread over the rows (the rank range's top: k = 64)"""
     rng = np.random.default_rng(11)
-    B = np.zeros((n, 3))
-    for c, (lo, hi) in enumerate([(0.05, 0.45), (0.3, 0.8), (0.55, 0.98)]):
+    spans = [(0.05, 0.45), (0.3, 0.8), (0.55, 0.98)]
+    if k != 3:
+        spans = [(lo, lo + 0.12) for lo in np.linspace(0.0, 0.87, k)]
+    B = np.zeros((n, k))
+    for c, (lo, hi) in enumerate(spans):
         rows = np.arange(int(lo * n), int(hi * n), 3)
         B[rows, c] = rng.uniform(0.5, 1.5, len(rows)) / len(rows)
-    return B, np.array([30.0, 80.0, 50.0])
+    return (B, np.array([30.0, 80.0, 50.0])) if k == 3 else (B, rng.uniform(20.0, 90.0, k))
 
 
-def _csr_worker(rank, world, port, which, omega, sweep_type, its, q, transport=None, lowrank=False):
+def _csr_worker(rank, world, port, which, omega, sweep_type, its, q, transport=None, lowrank=False, lowrank_k=3):
     import torch
     import torch.distributed as dist
 
@@ -246,7 +257,7 @@ def _csr_worker(rank, world, port, which, omega, sweep_type, its, q, transport=N
     smp = DistMCSOR(rp, A.colidx[sl], A.vals[sl], r0, r1, n, colors[r0:r1], int(colors.max()) + 1, rank, world, omega=omega, sweep_type=sweep_type, transport=transport)
     assert smp.transport == (transport or "torch") and (smp._c is not None) == (transport == "ipc")
     if lowrank:
-        B, S = _csr_lowrank_factors(n)
+        B, S = _csr_lowrank_factors(n, lowrank_k)
         smp.set_lowrank(B[r0:r1], S)
     rng = np.random.default_rng(5)
     b_all, y_all = rng.standard_normal(n), rng.standard_normal(n)
@@ -339,7 +350,7 @@ def _aij_mg_worker(rank, world, port, refine, coarse_max, opts, its, q):
     n = len(ops[-1][0]) - 1
     r0, r1 = mg.row_range
     if opts.get("lowrank"):
-        B, S = _csr_lowrank_factors(n)
+        B, S = _csr_lowrank_factors(n, opts.get("lowrank_k", 3))
         mg.set_lowrank(B[r0:r1], S)
     mg.setup()
     rng = np.random.default_rng(5)
@@ -363,11 +374,12 @@ def _aij_mg_worker(rank, world, port, refine, coarse_max, opts, its, q):
     (2, 300, 2, {"literal": True, "scaled": True}),
     (2, 300, 3, {"lowrank": True, "scaled": True, "sweep": 3}),
     (3, 500, 2, {"lowrank": True, "literal": True, "scaled": True}),
+    (2, 300, 3, {"lowrank": True, "lowrank_k": 64, "scaled": True, "sweep": 3}),               # the top of the rank range
     (3, 300, 3, {"replicate_below": 2000, "scaled": True, "sweep": 3}),                     # 5 levels: 114, 408, 1549 replicated, 6033 and 23809 by row blocks
     (3, 300, 2, {"replicate_below": 500, "lowrank": True, "scaled": True}),                  # the low-rank block is handed to the replicated levels at the fold
     (2, 300, 2, {"replicate_below": 10 ** 9}),                                                # only the finest level by row blocks
     (3, 300, 2, {"replicate_below": 2000, "scaled": True, "coloring": 3}),                   # PMG_COLORING_ITERATED on row-block and replicated levels (round 4)
-], ids=["1rank", "2ranks", "3ranks_symmetric_nu2", "4ranks_backward_4levels", "2ranks_literal", "3ranks_lowrank", "2ranks_lowrank_literal", "3ranks_replicated_small_levels", "2ranks_replicated_lowrank", "2ranks_only_finest_distributed", "2ranks_iterated_colouring"])
+], ids=["1rank", "2ranks", "3ranks_symmetric_nu2", "4ranks_backward_4levels", "2ranks_literal", "3ranks_lowrank", "2ranks_lowrank_literal", "3ranks_lowrank_k64", "3ranks_replicated_small_levels", "2ranks_replicated_lowrank", "2ranks_only_finest_distributed", "2ranks_iterated_colouring"])
 def test_row_block_distributed_aij_vcycle_reproduces_the_single_device_chain(refine, coarse_max, world, opts):
     """PCGAMGMC on a MATMPIAIJ hierarchy (reference src/pc_gamgmc.c:157-223 over MCSORApply_MPIAIJ, src/mc_sor.c:298-381):
     the aggregation hierarchy of the P1 matrix of the reference's lshape.msh, every level above the coarsest split into
@@ -402,7 +414,7 @@ def test_row_block_distributed_aij_vcycle_reproduces_the_single_device_chain(ref
     one.set_smoother(o["scaled"], o["omega"], o["sweep"], o["nu"])
     one.set_correction_form(o["literal"])
     if o.get("lowrank"):
-        one.set_lowrank(*_csr_lowrank_factors(n))
+        one.set_lowrank(*_csr_lowrank_factors(n, o.get("lowrank_k", 3)))
     one.setup()
     yd = torch.as_tensor(y_all, device="cuda")
     ctr = one.sample(torch.as_tensor(b_all, device="cuda"), yd, its, seed=42, counter0=1)
@@ -421,8 +433,8 @@ def test_row_block_distributed_aij_vcycle_reproduces_the_single_device_chain(ref
     assert np.array_equal(got, ref)
 
 
-@pytest.mark.parametrize("world,sweep_type", [(2, 1), (3, 3), (4, 2)], ids=["2ranks", "3ranks_symmetric", "4ranks_backward"])
-def test_row_block_sampler_with_a_low_rank_update(world, sweep_type):
+@pytest.mark.parametrize("world,sweep_type,k", [(2, 1, 3), (3, 3, 3), (4, 2, 3), (3, 3, 64)], ids=["2ranks", "3ranks_symmetric", "4ranks_backward", "3ranks_symmetric_k64"])
+def test_row_block_sampler_with_a_low_rank_update(world, sweep_type, k):
     """MATLRC operator A + B S B^T on a row-block distributed MATAIJ base (MCSORSetUp's LRC branch, reference
     src/mc_sor.c:572-595; per-sweep repair :101-112, noise term src/pc_mcgibbs.c:130-140): the correction is built with
     distributed deterministic sweeps and rank-ordered all-reduces, the k-vectors B^T y are summed per rank and then over
@@ -436,7 +448,7 @@ def test_row_block_sampler_with_a_low_rank_update(world, sweep_type):
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
-    procs = [ctx.Process(target=_csr_worker, args=(r, world, port, "lshape", omega, sweep_type, its, q, "ipc", True)) for r in range(world)]
+    procs = [ctx.Process(target=_csr_worker, args=(r, world, port, "lshape", omega, sweep_type, its, q, "ipc", True, k)) for r in range(world)]
     for p in procs:
         p.start()
     parts = sorted((q.get(timeout=150) for _ in range(world)), key=lambda t: t[0])
@@ -449,7 +461,7 @@ def test_row_block_sampler_with_a_low_rank_update(world, sweep_type):
     one = MCSOR(A.rowptr, A.colidx, A.vals, user_colors=colors).setup()
     one.set_omega(omega)
     one.set_sweep_type(sweep_type)
-    one.set_lowrank(*_csr_lowrank_factors(A.n))
+    one.set_lowrank(*_csr_lowrank_factors(A.n, k))
     yd = torch.as_tensor(y_all, device="cuda")
     ctr = one.sample(torch.as_tensor(b_all, device="cuda"), yd, its, seed=42, counter0=1)
     assert all(x[2] == ctr for x in parts)
