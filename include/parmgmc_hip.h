@@ -87,7 +87,11 @@ pmg_status pmg_mcsor_create_csr(int32_t n, const int32_t *rowptr_host, const int
 /* the same for either PetscInt width (idx_width = 32 | 64); 64-bit arrays are narrowed to checked 32-bit copies at once,
    so they need not outlive the call */
 pmg_status pmg_mcsor_create_csr_idx(int64_t n, const void *rowptr_host, const void *colidx_host, const double *vals_host, int idx_width, pmg_mcsor *mc);
-/* Choose the colouring before setup.  user_colors_host (n entries, colours 0..ncolors-1) only for USER. */
+/* Choose the colouring before setup.  user_colors_host (n entries, colours 0..ncolors-1) only for USER.  Whatever the rule,
+   pmg_mcsor_setup checks the colouring against the stored pattern and fails with PMG_ERR_ARG_WRONG, naming two coupled rows
+   of one colour, if it is not a distance-1 colouring.  GREEDY, ITERATED and LEXLEVELS only look at the columns a row lists:
+   they always pass on STRUCTURALLY SYMMETRIC patterns, and can fail on a pattern in which r lists c but c does not list r
+   (the sweep would read y[c] while c is being updated). */
 pmg_status pmg_mcsor_set_coloring(pmg_mcsor mc, int rule, const int32_t *user_colors_host);
 /* MCSORSetUp (src/mc_sor.c:553-605): diagonal pointers (:126-150), colouring (:441-454), idiag (:114-124);
    builds the colour-partitioned sliced-ELL copy and uploads it.  Synchronous. */

@@ -181,6 +181,22 @@ static pmg_status color_lexlevels(pmg_mcsor mc)
   return PMG_SUCCESS;
 }
 
+/* Is mc->colors a distance-1 colouring of the STORED pattern?  O(nnz).  The automatic rules only look at the columns a row
+   lists, so on a structurally non-symmetric pattern (r lists c, c does not list r) they can give r and c one colour; the
+   sweep would then read y[c] while c is being updated (a race, and not the oracle's order).  Refused, like a bad user
+   colouring and like pmg_rowblock_check_coloring. */
+static pmg_status coloring_check(pmg_mcsor mc)
+{
+  const char *rule = mc->rule == PMG_COLORING_GREEDY ? "greedy" : mc->rule == PMG_COLORING_ITERATED ? "iterated" : mc->rule == PMG_COLORING_LEXLEVELS ? "lexlevels" : "user";
+  for (int32_t r = 0; r < mc->n; ++r)
+    for (int32_t k = mc->rowptr[r]; k < mc->rowptr[r + 1]; ++k) {
+      const int32_t c = mc->colidx[k];
+      PMG_CHECK(c == r || mc->colors[c] != mc->colors[r], PMG_ERR_ARG_WRONG, "rows %d and %d are coupled but share colour %d: the %s colouring is not a distance-1 colouring%s", r, c, mc->colors[r], rule,
+                mc->rule == PMG_COLORING_USER ? " (use PMG_COLORING_LEXLEVELS for the serial one-colour behaviour)" : " (the pattern is not structurally symmetric)");
+    }
+  return PMG_SUCCESS;
+}
+
 static pmg_status color_user(pmg_mcsor mc)
 {
   int32_t nc = 0;
@@ -189,11 +205,6 @@ static pmg_status color_user(pmg_mcsor mc)
     mc->colors[r] = mc->user_colors[r];
     if (mc->colors[r] + 1 > nc) nc = mc->colors[r] + 1;
   }
-  for (int32_t r = 0; r < mc->n; ++r)
-    for (int32_t k = mc->rowptr[r]; k < mc->rowptr[r + 1]; ++k) {
-      const int32_t c = mc->colidx[k];
-      PMG_CHECK(c == r || mc->colors[c] != mc->colors[r], PMG_ERR_ARG_WRONG, "rows %d and %d are coupled but share colour %d: not a distance-1 colouring (use PMG_COLORING_LEXLEVELS for the serial one-colour behaviour)", r, c, mc->colors[r]);
-    }
   mc->ncolors = nc;
   return PMG_SUCCESS;
 }
@@ -351,8 +362,11 @@ pmg_status pmg_mcsor_setup(pmg_mcsor mc)
     PMG_FAIL(PMG_ERR_MEM, "out of host memory");
   }
   pmg_status st = mc->rule == PMG_COLORING_GREEDY ? color_greedy(mc) : mc->rule == PMG_COLORING_ITERATED ? color_iterated(mc) : mc->rule == PMG_COLORING_LEXLEVELS ? color_lexlevels(mc) : color_user(mc);
+  if (!st) st = coloring_check(mc); /* whatever the rule */
   if (st) {
     free(diagptr);
+    free(mc->colors);
+    mc->colors = NULL;
     return st;
   }
   const int32_t nc = mc->ncolors;

@@ -72,7 +72,17 @@ def _init(rank, world, port):
     dist.init_process_group("gloo", rank=rank, world_size=world)
 
 
-def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury, env=None):
+def _sampler_matrix(name):
+    """'lshape': the P1 matrix of lshape.msh refined once; 'hubs': tests/aij_workloads.py's 64 x 64 Laplacian with hub rows of
+    1000, 3000 and 100 random columns (rows 37, 2100, 4000: each of two ranks owns one, and their columns cross the boundary)"""
+    if name == "hubs":
+        from aij_workloads import hubs
+
+        return hubs()
+    return lshape(1)
+
+
+def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury, env=None, mat="lshape"):
     import torch
     import torch.distributed as dist
 
@@ -82,7 +92,7 @@ def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury, env=
         from parmgmc_amd.dist import CRowBlock
         from parmgmc_amd.wrappers import WoodburySampler
 
-        A = lshape(1)
+        A = _sampler_matrix(mat)
         n = A.shape[0]
         rs = np.array([round(n * r / world) for r in range(world + 1)], np.int64)
         mine = A[rs[rank]:rs[rank + 1]].tocsr()
@@ -120,16 +130,28 @@ def _sampler_worker(rank, world, port, q, omega, sweep_type, its, woodbury, env=
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,sweep_type,env", [(2, 1, {}), (3, 3, {}), (3, 2, {"PMG_DISTMCSOR_REFRESH_BY_COLOUR": "1"})], ids=["2ranks", "3ranks_symmetric", "3ranks_backward_refresh_by_colour"])
-def test_c_row_block_sampler_is_the_single_device_chain(world, sweep_type, env):
+@pytest.mark.parametrize(
+    "world,sweep_type,env,mat",
+    [(2, 1, {}, "lshape"), (3, 3, {}, "lshape"), (3, 2, {"PMG_DISTMCSOR_REFRESH_BY_COLOUR": "1"}, "lshape"), (2, 3, {}, "hubs")],
+    ids=["2ranks", "3ranks_symmetric", "3ranks_backward_refresh_by_colour", "2ranks_hubs_symmetric"],
+)
+def test_c_row_block_sampler_is_the_single_device_chain(world, sweep_type, env, mat):
     """env: PMG_DISTMCSOR_REFRESH_BY_COLOUR=1 refreshes the ghost rows colour by colour instead of in one all-gather"""
     import torch
 
     from parmgmc_amd import MCSOR
 
     omega, its = 1.15, 3
-    parts = _run(_sampler_worker, world, omega, sweep_type, its, False, env)
-    A = lshape(1)
+    parts = _run(_sampler_worker, world, omega, sweep_type, its, False, env, mat)
+    A = _sampler_matrix(mat)
+    if mat == "hubs":  # every rank owns a hub row, and each hub row has columns on the other rank
+        from aij_workloads import HUB_ROWS
+
+        half = round(A.shape[0] / 2)
+        for h in HUB_ROWS:
+            c = A.indices[A.indptr[h]:A.indptr[h + 1]]
+            assert np.diff(A.indptr)[h] > 100 and np.any(c < half) and np.any(c >= half)
+        assert {h < half for h in HUB_ROWS} == {True, False}
     rng = np.random.default_rng(5)
     b_all, y_all = rng.standard_normal(A.shape[0]), rng.standard_normal(A.shape[0])
     one = MCSOR(A.indptr, A.indices, A.data).setup()
@@ -207,16 +229,27 @@ def _hier_levels(ops, ps, rank, world):
     return out, n
 
 
-def _mgmc_worker(rank, world, port, q, lowrank, its):
+def _hierarchy(name):
+    """'lshape': plain aggregation of lshape.msh refined twice; 'sa3d25': tests/aij_workloads.py's smoothed-aggregation
+    hierarchy of the 7-point 25^3 Laplacian (operator rows of 207 entries, P^T rows of 2 980)"""
+    if name == "sa3d25":
+        from aij_workloads import hierarchy
+
+        return hierarchy("sa3d25")
+    from parmgmc_amd.unstructured import build_hierarchy
+
+    return build_hierarchy(lshape(2), coarse_max=60)
+
+
+def _mgmc_worker(rank, world, port, q, lowrank, its, hier="lshape"):
     import torch
     import torch.distributed as dist
 
     try:
         _init(rank, world, port)
         from parmgmc_amd.dist import CRowBlock
-        from parmgmc_amd.unstructured import build_hierarchy
 
-        ops, ps = build_hierarchy(lshape(2), coarse_max=60)
+        ops, ps = _hierarchy(hier)
         levels, n = _hier_levels(ops, ps, rank, world)
         r0, r1 = levels[-1]["row0"], levels[-1]["row0"] + len(levels[-1]["A"][0]) - 1
         lr = None
@@ -241,16 +274,19 @@ def _mgmc_worker(rank, world, port, q, lowrank, its):
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("world,lowrank", [(2, False), (3, False), (2, True)], ids=["2ranks", "3ranks", "2ranks_lowrank"])
-def test_c_row_block_hierarchy_is_the_single_device_chain(world, lowrank):
+@pytest.mark.parametrize(
+    "world,lowrank,hier",
+    [(2, False, "lshape"), (3, False, "lshape"), (2, True, "lshape"), (2, False, "sa3d25"), (3, False, "sa3d25")],
+    ids=["2ranks", "3ranks", "2ranks_lowrank", "2ranks_sa3d25", "3ranks_sa3d25"],
+)
+def test_c_row_block_hierarchy_is_the_single_device_chain(world, lowrank, hier):
     import torch
 
     from parmgmc_amd import MGMC
-    from parmgmc_amd.unstructured import build_hierarchy
 
     its = 3
-    parts = _run(_mgmc_worker, world, lowrank, its)
-    ops, ps = build_hierarchy(lshape(2), coarse_max=60)
+    parts = _run(_mgmc_worker, world, lowrank, its, hier)
+    ops, ps = _hierarchy(hier)
     n = len(ops[-1][0]) - 1
     rng = np.random.default_rng(5)
     b_all, y_all = rng.standard_normal(n), rng.standard_normal(n)
