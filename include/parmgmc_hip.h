@@ -135,11 +135,17 @@ pmg_status pmg_mcsor_residual_layout(pmg_mcsor mc, const double *b_lay, const do
    pmg_mcsor_apply / pmg_mcsor_sample on that column alone with seed = seeds_host[c]; *counter_out is the single-chain value.
    Per-chain workspace is allocated on first use, grows with nchains and lives until pmg_mcsor_destroy.
    PMG_ERR_ARG_OUTOFRANGE: nchains < 1 or sizes beyond 64-bit / launch limits; PMG_ERR_ARG_NULL: NULL seeds, b or Y;
-   PMG_ERR_ARG_WRONGSTATE: not set up (these checks run before any device work); PMG_ERR_SUP: a low-rank (MATLRC) update. */
+   PMG_ERR_ARG_WRONGSTATE: not set up (these checks run before any device work); PMG_ERR_SUP: the unscaled noise with omega != 1.
+   A low-rank (MATLRC) update (pmg_mcsor_set_lowrank, either storage form) is carried: every directional sweep of chain c adds
+   B (sqrt(S) o eta) with the key of seeds_host[c] to its right-hand side when noisy and is followed by the repair
+   y -= Bb (B^T y), as in the single-chain call; b comes back unchanged. */
 /* deterministic MCSORApply (src/mc_sor.c:216-239) on C chains */
 pmg_status pmg_mcsor_apply_chains(pmg_mcsor mc, int32_t nchains, const double *b_dev, double *Y_dev, void *stream);
 /* pmg_mcsor_sample (src/pc_mcgibbs.c:155-188, src/pc_sorgibbs.c:76-103) on C chains */
 pmg_status pmg_mcsor_sample_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds_host, const double *b_dev, double *Y_dev, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream);
+/* the same with ONE RIGHT-HAND SIDE PER CHAIN: B_nat_dev is n x nchains, chain fastest (the layout of Y); column c equals
+   pmg_mcsor_sample with b = B[:, c] and seed = seeds_host[c].  Checks and errors as pmg_mcsor_sample_chains. */
+pmg_status pmg_mcsor_sample_chains_rhs(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds_host, const double *B_nat_dev, double *Y_dev, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream);
 /* Building blocks of the ROW-BLOCK distributed sampler (MCSORApply_MPIAIJ, src/mc_sor.c:298-381: for every colour,
    update the ghost values, then sweep the colour's rows): a rank holds its rows with the off-process columns appended
    as ghost rows (identity rows in an extra, never swept colour); the caller moves ghost values between the per-colour
@@ -439,6 +445,9 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc mg, double *total, double *pe
    hierarchies (pmg_mgmc_create_dmda*), row-block hierarchies, a low-rank update; other errors as pmg_mcsor_sample_chains. */
 typedef int (*pmg_chains_callback)(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
 pmg_status pmg_mgmc_sample_chains(pmg_mgmc mg, int32_t nchains, const uint64_t *seeds_host, const double *b_nat_dev, double *Y_nat_dev, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
+/* the same with ONE RIGHT-HAND SIDE PER CHAIN: B_nat_dev is n x nchains, chain fastest; column c equals pmg_mgmc_sample with
+   b = B[:, c] -- the prior sampler under pmg_woodbury_noisy_rhs_chains.  Checks and errors as pmg_mgmc_sample_chains. */
+pmg_status pmg_mgmc_sample_chains_rhs(pmg_mgmc mg, int32_t nchains, const uint64_t *seeds_host, const double *B_nat_dev, double *Y_nat_dev, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
 /* algorithmic bytes of ONE V-cycle advancing all C chains (the chains analogue of pmg_mgmc_get_algorithmic_bytes): shared
    operands (matrices, idiag, sqrtdiag, the shared b, P, W) counted once, iterates and per-chain right-hand sides C times */
 pmg_status pmg_mgmc_get_algorithmic_bytes_chains(pmg_mgmc mg, int32_t nchains, double *total, double *per_level_host);
@@ -571,6 +580,11 @@ pmg_status pmg_woodbury_set_c_column(pmg_woodbury w, int32_t c, const double *x_
 pmg_status pmg_woodbury_finish(pmg_woodbury w);
 pmg_status pmg_woodbury_noisy_rhs(pmg_woodbury w, const double *b_dev, double *w_dev, uint64_t seed, uint64_t counter, void *stream);
 pmg_status pmg_woodbury_correct(pmg_woodbury w, double *y_dev, void *stream);
+/* the sample step on C CHAINS (one device): W_dev and Y_dev are n x nchains, chain fastest, b_dev one vector shared by the
+   chains.  Column c of W equals pmg_woodbury_noisy_rhs with seed = seeds_host[c]; column c of Y after the correction equals
+   pmg_woodbury_correct on that column.  PMG_ERR_SUP: an object built with a pmg_dist. */
+pmg_status pmg_woodbury_noisy_rhs_chains(pmg_woodbury w, int32_t nchains, const uint64_t *seeds_host, uint64_t counter, const double *b_dev, double *W_dev, void *stream);
+pmg_status pmg_woodbury_correct_chains(pmg_woodbury w, int32_t nchains, double *Y_dev, void *stream);
 pmg_status pmg_woodbury_get_correction(pmg_woodbury w, double *G_host);
 pmg_status pmg_woodbury_destroy(pmg_woodbury *w);
 

@@ -269,6 +269,10 @@ _sig = {
     "pmg_mcsor_sample_chains": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp]),
     "pmg_mgmc_sample_chains": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
     "pmg_mgmc_get_algorithmic_bytes_chains": (_int, [_vp, _i32, C.POINTER(_dbl), _vp]),
+    "pmg_mcsor_sample_chains_rhs": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp]),
+    "pmg_mgmc_sample_chains_rhs": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
+    "pmg_woodbury_noisy_rhs_chains": (_int, [_vp, _i32, _vp, _u64, _vp, _vp, _vp]),
+    "pmg_woodbury_correct_chains": (_int, [_vp, _i32, _vp, _vp]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

@@ -70,6 +70,9 @@ void       pmg_lrc_get_sizes(pmg_lrc l, int32_t *k, int64_t *ns, int *dense); /*
 pmg_status pmg_lrc_get_compact(pmg_lrc l, int32_t *k, int64_t *ns, int64_t *rows_host, double *B_host, double *Bbf_host, double *Bbb_host);
 pmg_lrc    pmg_grid_lrc(pmg_grid g); /* the grid operator's low-rank update, NULL if none (borrowed) */
 void       pmg_lrc_destroy(pmg_lrc *l);
+/* the noise term and the repair on C chains (ld x C, chain fastest): pmg_lrc_rhs into out (b chain stride b_cs) / pmg_lrc_post per column */
+pmg_status pmg_lrc_rhs_chains(pmg_lrc l, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *b_lay, int b_cs, double *out_lay, void *stream);
+pmg_status pmg_lrc_post_chains(pmg_lrc l, int32_t nchains, int dir, double *Y_lay, void *stream);
 pmg_status pmg_mcsor_set_idiag_by_division(pmg_mcsor mc, int on); /* PCPARSOR's idiag = omega / d */
 pmg_status pmg_mcsor_set_natural_order(pmg_mcsor mc, int on); /* no locality renumbering inside the colours (hierarchy levels) */
 /* pmg_parsor.c: data-flow form of PCPARSOR's multi-rank sweep; the four arrays are malloc'ed, the caller frees them */

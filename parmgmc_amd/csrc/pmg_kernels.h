@@ -198,6 +198,12 @@ int pmgk_permute_out_chains(int32_t ld, const int32_t *orig, int32_t nchains, co
 int pmgk_csr_spmv_rows_chains(int32_t nrows, const int32_t *rowpos, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t nchains, const double *X, double *Y, int accumulate, double *zero, void *stream);
 int pmgk_fill_normal_rows_chains(int64_t n, int32_t nchains, const uint64_t *keys, uint64_t sweep, double *Xi, void *stream);
 int pmgk_tri_gemv_chains(int32_t n, int upper, const double *M, int32_t nchains, const double *X, const double *Add, double *Out, void *stream);
+/* the low-rank pieces on many chains (kernels_lrc_chains.hip); k-vectors of the chains are k x C, chain fastest.  rows != NULL:
+   the row-compact form (M over the support rows, vectors indexed at rows[q]), else the dense form over all rows */
+int pmgk_lrc_btx_chains_nblocks(int64_t n, int compact);
+int pmgk_lrc_btx_chains(int64_t n, const int64_t *rows, int k, const double *M, int64_t ldm, const double *Y, int32_t nchains, double *partial, const double *scale, double *out, void *stream);
+int pmgk_lrc_axpy_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, void *stream);
+int pmgk_lrc_noise_chains(int k, int32_t nchains, const uint64_t *keys, uint64_t tag, uint64_t sweep, const double *sqrtS, double *eta, void *stream);
 
 #ifdef __cplusplus
 }

@@ -53,6 +53,9 @@ struct pmg_lrc_s {
   int      empty;            /* this rank's rows do not meet the support of B at all (row-distributed operator) */
   pmg_lrc_reduce_fn reduce;  /* row-distributed operator: sum of the k-vectors over the ranks */
   void             *rctx;
+  /* many chains (pmg_lrc_rhs_chains / pmg_lrc_post_chains): k x ch_cap k-vectors and the block sums of B^T Y, first use */
+  int32_t ch_cap;
+  double *ch_eta, *ch_wk, *ch_partial;
 };
 
 void pmg_lrc_destroy(pmg_lrc *p)
@@ -75,6 +78,9 @@ void pmg_lrc_destroy(pmg_lrc *p)
   pmg_dev_free(l->Bbc[0]);
   pmg_dev_free(l->Bbc[1]);
   pmg_dev_free(l->saved);
+  pmg_dev_free(l->ch_eta);
+  pmg_dev_free(l->ch_wk);
+  pmg_dev_free(l->ch_partial);
   free(l);
   *p = NULL;
 }
@@ -484,5 +490,57 @@ pmg_status pmg_lrc_post(pmg_lrc l, int dir, double *y_lay, void *stream)
   PMG_KERNEL(pmgk_lrc_btx(l->ld, l->k, l->B, l->ld, y_lay, l->partial, NULL, l->wk, stream));
   if (l->reduce) PMG_CALL(l->reduce(l->rctx, l->wk, l->k, stream));
   PMG_KERNEL(pmgk_lrc_axpy_cols(l->ld, l->k, l->Bb[d], l->ld, l->wk, -1.0, y_lay, y_lay, stream));
+  return PMG_SUCCESS;
+}
+
+/* ---- many chains of one operator (pmg_mcsor_sample_chains / pmg_mcsor_apply_chains): Y and the right-hand sides are ld x C
+   doubles in the layout, chain fastest.  Column c performs the single-chain calls' arithmetic (kernels_lrc_chains.hip): the
+   noise term of pmg_lrc_rhs with the key pmg_lrc_noise_seed(keys[c]) and the repair of pmg_lrc_post, in both storage forms. */
+static pmg_status lrc_chains_workspace(pmg_lrc l, int32_t C, void *stream)
+{
+  PMG_CHECK(pmg_lrc_is_local(l), PMG_ERR_SUP, "the chain forms of the low-rank update need an update on one device");
+  if (C <= l->ch_cap) return PMG_SUCCESS;
+  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffers may still be in use */
+  pmg_dev_free(l->ch_eta);
+  pmg_dev_free(l->ch_wk);
+  pmg_dev_free(l->ch_partial);
+  l->ch_eta = l->ch_wk = l->ch_partial = NULL;
+  l->ch_cap                            = 0;
+  const size_t kc = (size_t)l->k * (size_t)C;
+  const int    nb = pmgk_lrc_btx_chains_nblocks(l->ns ? l->ns : l->ld, l->ns > 0);
+  PMG_CALL(pmg_dev_alloc((void **)&l->ch_eta, sizeof(double) * kc));
+  PMG_CALL(pmg_dev_alloc((void **)&l->ch_wk, sizeof(double) * kc));
+  PMG_CALL(pmg_dev_alloc((void **)&l->ch_partial, sizeof(double) * kc * (size_t)nb));
+  l->ch_cap = C;
+  return PMG_SUCCESS;
+}
+
+/* the right-hand sides of a noisy sweep on C chains: out = b + B (sqrt(S) o eta_c) on the support rows (every row in the dense
+   form), eta_c the k normals of (pmg_lrc_noise_seed(keys[c]), counter); b has chain stride b_cs (0: one vector for all chains).
+   The other rows of out are left alone: the caller fills them with b once. */
+pmg_status pmg_lrc_rhs_chains(pmg_lrc l, int32_t C, const uint64_t *keys_dev, uint64_t counter, const double *b_lay, int b_cs, double *out_lay, void *stream)
+{
+  PMG_CALL(lrc_chains_workspace(l, C, stream));
+  PMG_CALL(lrc_flush_restore(l, stream));
+  PMG_KERNEL(pmgk_lrc_noise_chains(l->k, C, keys_dev, pmg_lrc_noise_seed(0), counter, l->sqrtS, l->ch_eta, stream));
+  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bc, l->ns, l->ch_eta, 1.0, b_lay, b_cs, out_lay, C, stream));
+  else PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->B, l->ld, l->ch_eta, 1.0, b_lay, b_cs, out_lay, C, stream));
+  return PMG_SUCCESS;
+}
+
+/* Y -= Bb_dir (B^T Y) on C chains (pmg_lrc_post per column) */
+pmg_status pmg_lrc_post_chains(pmg_lrc l, int32_t C, int dir, double *Y_lay, void *stream)
+{
+  const int d = dir == PMG_SOR_FORWARD_SWEEP ? 0 : 1;
+  PMG_CALL(lrc_chains_workspace(l, C, stream));
+  PMG_CALL(lrc_flush_restore(l, stream));
+  l->bty_vec = NULL;
+  if (l->ns) {
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, Y_lay, C, l->ch_partial, NULL, l->ch_wk, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bbc[d], l->ns, l->ch_wk, -1.0, Y_lay, 1, Y_lay, C, stream));
+  } else {
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, Y_lay, C, l->ch_partial, NULL, l->ch_wk, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->Bb[d], l->ld, l->ch_wk, -1.0, Y_lay, 1, Y_lay, C, stream));
+  }
   return PMG_SUCCESS;
 }

@@ -42,6 +42,9 @@ struct pmg_mcsor_s {
   double    *ch_b;    /* [ld] the shared right-hand side in the layout */
   double    *ch_Y;    /* [ld * ch_cap] the chains in the layout, chain fastest */
   pmg_keybuf ch_keys; /* the chains' noise keys */
+  int32_t    ch_B_cap, ch_bc_cap;
+  double    *ch_B;  /* [ld * ch_B_cap] one right-hand side per chain in the layout (pmg_mcsor_sample_chains_rhs) */
+  double    *ch_bc; /* [ld * ch_bc_cap] the right-hand sides of a noisy sweep with the low-rank noise term */
 };
 
 /* --- colouring rules -------------------------------------------------------------------------------- */
@@ -270,9 +273,11 @@ static void mcsor_free_chains(pmg_mcsor mc)
 {
   pmg_dev_free(mc->ch_b);
   pmg_dev_free(mc->ch_Y);
+  pmg_dev_free(mc->ch_B);
+  pmg_dev_free(mc->ch_bc);
   pmg_keybuf_free(&mc->ch_keys);
-  mc->ch_b = mc->ch_Y = NULL;
-  mc->ch_cap          = 0;
+  mc->ch_b = mc->ch_Y = mc->ch_B = mc->ch_bc = NULL;
+  mc->ch_cap = mc->ch_B_cap = mc->ch_bc_cap = 0;
 }
 
 static void mcsor_free_setup(pmg_mcsor mc)
@@ -782,6 +787,7 @@ pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains)
   return PMG_SUCCESS;
 }
 
+/* what the V-cycle of the chains carries (pmg_mgmc_sample_chains); the MCSOR entry points take the low-rank update themselves */
 pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc)
 {
   PMG_CHECK(!mc->lrc, PMG_ERR_SUP, "multi-chain sampling of an operator with a low-rank (MATLRC) update is not supported");
@@ -792,6 +798,21 @@ const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc) { return mc->S.orig; }
 
 /* `its` times the directional sweeps of the sweep type (symmetric = forward + backward), every directional sweep with the next
    counter when noisy: pmg_mcsor_sample_layout / pmg_mcsor_apply_layout on C chains */
+/* one directional sweep over all colours on C chains */
+static pmg_status mcsor_dir_chains(pmg_mcsor mc, const pmgk_sell *S, int dir, int32_t nchains, const uint64_t *keys_dev, int noisy, uint64_t sweep, const double *b_lay, int bcs, double *Y_lay, void *stream)
+{
+  int rc = 0;
+  pmg_trace_begin(PMG_EVENT_MULTICOL_SOR);
+  if (dir == PMG_SOR_FORWARD_SWEEP) {
+    for (int32_t c = 0; c < mc->ncolors && !rc; ++c) rc = pmgk_sell_color_sweep_chains(S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
+  } else {
+    for (int32_t c = mc->ncolors - 1; c >= 0 && !rc; --c) rc = pmgk_sell_color_sweep_chains(S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
+  }
+  pmg_trace_end();
+  PMG_KERNEL(rc);
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *Y_lay, void *stream)
 {
   PMG_CALL(mcsor_ready(mc));
@@ -803,15 +824,30 @@ pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t
     for (int d = 0; d < ndir; ++d) {
       const int      dir   = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
       const uint64_t sweep = noisy ? ctr++ : 0;
-      int            rc    = 0;
-      pmg_trace_begin(PMG_EVENT_MULTICOL_SOR);
-      if (dir == PMG_SOR_FORWARD_SWEEP) {
-        for (int32_t c = 0; c < mc->ncolors && !rc; ++c) rc = pmgk_sell_color_sweep_chains(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
-      } else {
-        for (int32_t c = mc->ncolors - 1; c >= 0 && !rc; --c) rc = pmgk_sell_color_sweep_chains(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
-      }
-      pmg_trace_end();
-      PMG_KERNEL(rc);
+      PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, noisy, sweep, b_lay, bcs, Y_lay, stream));
+    }
+  }
+  if (counter_out) *counter_out = ctr;
+  return PMG_SUCCESS;
+}
+
+/* pmg_mcsor_sweeps_chains on an operator with a low-rank update, every directional sweep as mcsor_sweep_lrc per column: a noisy
+   sweep runs on rhs_lay (ld x C), whose support rows get b + B (sqrt(S) o eta_c) first (the caller has filled the other rows
+   with b); then the repair y -= Bb (B^T y) */
+static pmg_status mcsor_sweeps_lrc_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *rhs_lay, double *Y_lay, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  pmgk_sell S = mc->S;
+  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
+  uint64_t ctr = counter0;
+  for (int32_t it = 0; it < its; ++it) {
+    const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+    for (int d = 0; d < ndir; ++d) {
+      const int      dir   = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
+      const uint64_t sweep = noisy ? ctr++ : 0;
+      if (noisy) PMG_CALL(pmg_lrc_rhs_chains(mc->lrc, nchains, keys_dev, sweep, b_lay, bcs, rhs_lay, stream));
+      PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, noisy, sweep, noisy ? rhs_lay : b_lay, noisy ? 1 : bcs, Y_lay, stream));
+      PMG_CALL(pmg_lrc_post_chains(mc->lrc, nchains, dir, Y_lay, stream));
     }
   }
   if (counter_out) *counter_out = ctr;
@@ -845,22 +881,54 @@ static pmg_status mcsor_chains_args(pmg_mcsor mc, int32_t nchains, int need_seed
   PMG_CHECK(mc, PMG_ERR_ARG_NULL, "null MCSOR");
   PMG_CHECK(nchains >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", nchains);
   PMG_CHECK(b && Y && (seeds || !need_seeds), PMG_ERR_ARG_NULL, "null argument");
-  PMG_CALL(pmg_mcsor_chains_supported(mc));
   PMG_CHECK(mc->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_mcsor_setup first");
   return pmg_chains_size_check(mc->S.ld, nchains);
+}
+
+/* ld x C layout buffer of its own capacity */
+static pmg_status mcsor_chains_buf(pmg_mcsor mc, double **buf, int32_t *cap, int32_t nchains, void *stream)
+{
+  if (nchains <= *cap) return PMG_SUCCESS;
+  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
+  pmg_dev_free(*buf);
+  *buf = NULL;
+  *cap = 0;
+  PMG_CALL(pmg_dev_alloc((void **)buf, sizeof(double) * (size_t)mc->S.ld * (size_t)nchains));
+  *cap = nchains;
+  return PMG_SUCCESS;
+}
+
+/* the chains entry points: right-hand side b_nat shared (bcs = 0, n values) or one per chain (bcs = 1, n x C, chain fastest) */
+static pmg_status mcsor_chains_run(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds, int noisy, const double *b_nat, int bcs, double *Y, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
+  if (noisy) PMG_CALL(pmg_keybuf_set(&mc->ch_keys, seeds, nchains, stream));
+  const double *b_lay = mc->ch_b;
+  if (bcs) {
+    PMG_CALL(mcsor_chains_buf(mc, &mc->ch_B, &mc->ch_B_cap, nchains, stream));
+    PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, 1, mc->ch_B, stream));
+    b_lay = mc->ch_B;
+  } else PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b_nat, mc->ch_b, stream));
+  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
+  const uint64_t *keys = noisy ? mc->ch_keys.dev : NULL;
+  if (!mc->lrc) PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_Y, stream));
+  else {
+    if (noisy) { /* the noisy sweeps' right-hand sides: b everywhere, the support rows rewritten before every sweep */
+      PMG_CALL(mcsor_chains_buf(mc, &mc->ch_bc, &mc->ch_bc_cap, nchains, stream));
+      PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, bcs, mc->ch_bc, stream));
+    }
+    PMG_CALL(mcsor_sweeps_lrc_chains(mc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_bc, mc->ch_Y, stream));
+  }
+  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
+  return PMG_SUCCESS;
 }
 
 /* the deterministic sweep of the current type on every chain (pmg_mcsor_apply per column) */
 pmg_status pmg_mcsor_apply_chains(pmg_mcsor mc, int32_t nchains, const double *b, double *Y, void *stream)
 {
   PMG_CALL(mcsor_chains_args(mc, nchains, 0, NULL, b, Y));
-  PMG_CALL(mcsor_ready(mc));
-  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
-  PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->ch_b, stream));
-  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
-  PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, NULL, 0, 0, 1, 0, NULL, mc->ch_b, 0, mc->ch_Y, stream));
-  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
-  return PMG_SUCCESS;
+  return mcsor_chains_run(mc, nchains, NULL, 0, b, 0, Y, 1, 0, 0, NULL, stream);
 }
 
 /* pmg_mcsor_sample per column: chain c with seed seeds[c], draw d of the call with counter counter0 + d */
@@ -869,14 +937,16 @@ pmg_status pmg_mcsor_sample_chains(pmg_mcsor mc, int32_t nchains, const uint64_t
   PMG_CALL(mcsor_chains_args(mc, nchains, 1, seeds, b, Y));
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
   PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
-  PMG_CALL(mcsor_ready(mc));
-  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
-  PMG_CALL(pmg_keybuf_set(&mc->ch_keys, seeds, nchains, stream));
-  PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->ch_b, stream));
-  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
-  PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, mc->ch_keys.dev, 1, scaled, its, counter0, counter_out, mc->ch_b, 0, mc->ch_Y, stream));
-  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
-  return PMG_SUCCESS;
+  return mcsor_chains_run(mc, nchains, seeds, 1, b, 0, Y, its, scaled, counter0, counter_out, stream);
+}
+
+/* pmg_mcsor_sample_chains with one right-hand side per chain: B is n x C, chain fastest; column c = pmg_mcsor_sample with b = B[:, c] */
+pmg_status pmg_mcsor_sample_chains_rhs(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds, const double *B, double *Y, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream)
+{
+  PMG_CALL(mcsor_chains_args(mc, nchains, 1, seeds, B, Y));
+  PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
+  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  return mcsor_chains_run(mc, nchains, seeds, 1, B, 1, Y, its, scaled, counter0, counter_out, stream);
 }
 
 /* the CSR arrays pmg_mcsor_create_csr borrowed become the object's (malloc'd by the caller, freed with the object) */

@@ -112,6 +112,8 @@ struct pmg_mgmc_s {
   double    *ch_Y, *ch_bs;       /* the chains' iterate and the shared right-hand side in the finest level's layout */
   double    *ch_xi, *ch_v;       /* exact coarse sampler: noise and L^-1 b + xi, n_0 x ch_cap */
   pmg_keybuf ch_keys;            /* level_seed(seeds[c], l) at l * C + c */
+  double    *ch_B;               /* one right-hand side per chain in the finest level's layout (pmg_mgmc_sample_chains_rhs), ld x ch_B_cap */
+  int32_t    ch_B_cap;
 };
 
 typedef struct {
@@ -1984,10 +1986,11 @@ static void mgmc_free_chains(pmg_mgmc h)
   pmg_dev_free(h->ch_bs);
   pmg_dev_free(h->ch_xi);
   pmg_dev_free(h->ch_v);
+  pmg_dev_free(h->ch_B);
   pmg_keybuf_free(&h->ch_keys);
   h->ch_b = h->ch_x = h->ch_r = NULL;
-  h->ch_Y = h->ch_bs = h->ch_xi = h->ch_v = NULL;
-  h->ch_cap                               = 0;
+  h->ch_Y = h->ch_bs = h->ch_xi = h->ch_v = h->ch_B = NULL;
+  h->ch_cap = h->ch_B_cap = 0;
 }
 
 static pmg_status mgmc_chains_workspace(pmg_mgmc h, int32_t C, void *stream)
@@ -2077,7 +2080,8 @@ static pmg_status mgmc_chains_check(pmg_mgmc h, int32_t C)
   return PMG_SUCCESS;
 }
 
-pmg_status pmg_mgmc_sample_chains(pmg_mgmc h, int32_t C, const uint64_t *seeds, const double *b_nat, double *Y_nat, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+/* the chains loop: right-hand side b_nat shared (bcs = 0, n values) or one per chain (bcs = 1, n x C, chain fastest) */
+static pmg_status mgmc_chains_run(pmg_mgmc h, int32_t C, const uint64_t *seeds, const double *b_nat, int bcs, double *Y_nat, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
 {
   PMG_CHECK(h, PMG_ERR_ARG_NULL, "null handle");
   PMG_CHECK(C >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", C);
@@ -2087,6 +2091,14 @@ pmg_status pmg_mgmc_sample_chains(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   const int top = h->nlevels - 1;
   mg_level *F   = &h->lv[top];
   PMG_CALL(mgmc_chains_workspace(h, C, stream));
+  if (bcs && C > h->ch_B_cap) { /* after the workspace: growing it frees this buffer too */
+    PMG_HIP(hipStreamSynchronize((hipStream_t)stream));
+    pmg_dev_free(h->ch_B);
+    h->ch_B     = NULL;
+    h->ch_B_cap = 0;
+    PMG_CALL(pmg_dev_alloc((void **)&h->ch_B, sizeof(double) * (size_t)F->ld * (size_t)C));
+    h->ch_B_cap = C;
+  }
   uint64_t *kh = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)h->nlevels * (size_t)C);
   PMG_CHECK(kh, PMG_ERR_MEM, "out of host memory");
   for (int l = 0; l <= top; ++l)
@@ -2097,14 +2109,16 @@ pmg_status pmg_mgmc_sample_chains(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   const uint64_t *keys = h->ch_keys.dev;
   const int32_t  *orig = pmg_mcsor_orig_dev(F->mc);
   const int64_t   nel  = F->ld * C;
-  PMG_KERNEL(pmgk_permute_in(F->ld, orig, b_nat, h->ch_bs, stream));
+  const double   *btop = bcs ? h->ch_B : h->ch_bs;
+  if (bcs) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 1, h->ch_B, stream));
+  else PMG_KERNEL(pmgk_permute_in(F->ld, orig, b_nat, h->ch_bs, stream));
   PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, Y_nat, 1, h->ch_Y, stream));
   for (int32_t it = 0; it < its; ++it) {
     const uint64_t sample = counter0 + (uint64_t)it;
     if (!h->correction_form || (it == 0 && guesszero)) /* in place on (b, Y), pmg_mgmc_sample's default; or Y = MG(b) (src/pc_gamgmc.c:243-246) */
-      PMG_CALL(mg_vcycle_chains(h, C, keys, h->ch_bs, 0, h->ch_Y, sample, !h->correction_form && !(it == 0 && guesszero), stream));
+      PMG_CALL(mg_vcycle_chains(h, C, keys, btop, bcs, h->ch_Y, sample, !h->correction_form && !(it == 0 && guesszero), stream));
     else { /* w = b - A y; work = MG(w); y += work, src/pc_gamgmc.c:253-256 */
-      PMG_CALL(pmg_mcsor_residual_chains(F->mc, C, h->ch_bs, 0, h->ch_Y, h->ch_b[top], stream));
+      PMG_CALL(pmg_mcsor_residual_chains(F->mc, C, btop, bcs, h->ch_Y, h->ch_b[top], stream));
       PMG_CALL(mg_vcycle_chains(h, C, keys, h->ch_b[top], 1, h->ch_x[top], sample, 0, stream));
       PMG_KERNEL(pmgk_axpy(nel, 1.0, h->ch_x[top], h->ch_Y, stream));
     }
@@ -2117,6 +2131,17 @@ pmg_status pmg_mgmc_sample_chains(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   PMG_KERNEL(pmgk_permute_out_chains(F->ld, orig, C, h->ch_Y, Y_nat, stream));
   if (counter_out) *counter_out = counter0 + (uint64_t)its;
   return PMG_SUCCESS;
+}
+
+pmg_status pmg_mgmc_sample_chains(pmg_mgmc h, int32_t C, const uint64_t *seeds, const double *b_nat, double *Y_nat, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+{
+  return mgmc_chains_run(h, C, seeds, b_nat, 0, Y_nat, its, guesszero, counter0, counter_out, cb, cbctx, stream);
+}
+
+/* pmg_mgmc_sample_chains with one right-hand side per chain (B_nat n x C, chain fastest): column c = pmg_mgmc_sample with b = B[:, c] */
+pmg_status pmg_mgmc_sample_chains_rhs(pmg_mgmc h, int32_t C, const uint64_t *seeds, const double *B_nat, double *Y_nat, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+{
+  return mgmc_chains_run(h, C, seeds, B_nat, 1, Y_nat, its, guesszero, counter0, counter_out, cb, cbctx, stream);
 }
 
 /* ALGORITHMIC bytes of ONE V-cycle of pmg_mgmc_sample_chains advancing all C chains, each launch counted once with its operands

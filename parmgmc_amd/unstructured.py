@@ -108,3 +108,14 @@ def build_hierarchy(A, coarse_max: int = 2000, max_levels: int = 12):
     operators = [(m.indptr.astype(np.int32), m.indices.astype(np.int32), m.data) for m in ops]
     interpolations = [None] + [(p.indptr.astype(np.int32), p.indices.astype(np.int32), p.data) for p in ps]
     return operators, interpolations
+
+
+def ball_observations(xy, centres, radius):
+    """observation vectors of balls on the mesh (the reference's ball indicators, src/obs.c:39-50, on mesh vertices instead
+    of grid points): column j is the indicator of the vertices within `radius` of centres[j], divided by their count"""
+    xy = np.asarray(xy, np.float64)
+    B = np.zeros((len(xy), len(centres)))
+    for j, ctr in enumerate(centres):
+        inside = ((xy - np.asarray(ctr, np.float64)) ** 2).sum(1) <= radius * radius
+        B[inside, j] = 1.0 / max(1, int(inside.sum()))
+    return B

@@ -31,6 +31,15 @@ def _chains(Y, n):
     return _ptr(Y), int(Y.shape[1])
 
 
+def _per_chain_rhs(b, n, nchains):
+    """True for one right-hand side per chain ((n, C), chain fastest), False for one shared vector (n,)"""
+    if b.dim() == 1:
+        assert b.shape[0] == n, f"need b of shape ({n},) or ({n}, {nchains})"
+        return False
+    assert tuple(b.shape) == (n, nchains), f"need b of shape ({n},) or ({n}, {nchains})"
+    return True
+
+
 def _seeds(seeds, nchains):
     s = np.ascontiguousarray([int(v) & 0xFFFFFFFFFFFFFFFF for v in seeds], np.uint64)
     assert len(s) == nchains, f"{len(s)} seeds for {nchains} chains"
@@ -105,11 +114,13 @@ class MCSOR:
         check(lib.pmg_mcsor_apply_chains(self._h, nc, _ptr(b), p, _stream()))
 
     def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, scaled: bool = True) -> int:
-        """`its` samples of C chains; column c equals sample(b, Y[:, c], its, seeds[c], counter0, scaled) bit for bit"""
+        """`its` samples of C chains; column c equals sample(b, Y[:, c], its, seeds[c], counter0, scaled) bit for bit.  b: one
+        vector (n,) shared by the chains, or one right-hand side per chain (n, C), column c = b[:, c]"""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
-        check(lib.pmg_mcsor_sample_chains(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(scaled), counter0, C.byref(out), _stream()))
+        fn = lib.pmg_mcsor_sample_chains_rhs if _per_chain_rhs(b, self.n, nc) else lib.pmg_mcsor_sample_chains
+        check(fn(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(scaled), counter0, C.byref(out), _stream()))
         return out.value
 
     # --- storage layout and per-colour sweeps (building blocks of the row-block distributed sampler) ---
@@ -443,8 +454,8 @@ class MGMC:
 
     def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None) -> int:
         """`its` samples of C chains on a hierarchy from from_hierarchy: Y is a contiguous (n, C) float64 tensor, b one vector
-        shared by all chains; column c equals sample(b, Y[:, c], its, seeds[c], ...) bit for bit.  callback(it, Y) after
-        every sample; a raised exception aborts the loop."""
+        (n,) shared by all chains or one per chain (n, C); column c equals sample(b or b[:, c], Y[:, c], its, seeds[c], ...) bit
+        for bit.  callback(it, Y) after every sample; a raised exception aborts the loop."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
@@ -462,7 +473,8 @@ class MGMC:
                     return 77
 
             cb = capi.CHAINS_CALLBACK(_cb)
-        check(lib.pmg_mgmc_sample_chains(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(guesszero), counter0, C.byref(out), cb, None, _stream()))
+        fn = lib.pmg_mgmc_sample_chains_rhs if _per_chain_rhs(b, self.n, nc) else lib.pmg_mgmc_sample_chains
+        check(fn(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(guesszero), counter0, C.byref(out), cb, None, _stream()))
         return out.value
 
     def algorithmic_bytes_chains(self, nchains: int):
@@ -488,9 +500,10 @@ class WoodburySampler:
     on one device or on rows distributed over ranks (z-slabs, row blocks): B_rows = this rank's rows of B (n x k), vectors in
     natural order over those rows; `dist_handle` = the C handle of a transport of the ranks (ctypes void pointer) or None.
       solve(b, x)            x <- (approximately) A^-1 b from the zero guess x holds (device tensors), collective
-      sample(w, y, counter)  one sample of the A-sampler on right-hand side w, y updated in place, collective"""
+      sample(w, y, counter)  one sample of the A-sampler on right-hand side w, y updated in place, collective
+      sample_chains(W, Y, counter)  (optional, one device) the same on C chains: column c of Y advanced on W[:, c] (run_chains)"""
 
-    def __init__(self, B_rows, S, solve, sample, dist_handle=None):
+    def __init__(self, B_rows, S, solve, sample, dist_handle=None, sample_chains=None):
         import torch
 
         B = np.asfortranarray(B_rows, np.float64)
@@ -499,6 +512,8 @@ class WoodburySampler:
         assert len(S) == self.k
         self._h = C.c_void_p()
         self._sample = sample
+        self._sample_chains = sample_chains
+        self._W = None
         check(lib.pmg_woodbury_create(self.n, self.k, B.ctypes.data, max(self.n, 1), S.ctypes.data, dist_handle, C.byref(self._h)))
         for c in range(self.k):  # C = solver(B) column by column from a zero guess (src/woodbury.c:35-50)
             b = torch.as_tensor(np.ascontiguousarray(B[:, c]), device="cuda")
@@ -523,6 +538,27 @@ class WoodburySampler:
             check(lib.pmg_woodbury_correct(self._h, _ptr(y), _stream()))
             if callback is not None:
                 callback(it, y)
+        return counter0 + its
+
+    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None) -> int:
+        """run() on C chains of one device: Y is a contiguous (n, C) float64 tensor, b one vector (n,) shared by the chains;
+        column c equals run(b, Y[:, c], its, seeds[c], counter0) bit for bit when sample_chains(W, Y, counter) advances every
+        column c of Y as sample(W[:, c], Y[:, c], counter) does -- e.g. MGMC.sample_chains with per-chain right-hand sides.
+        callback(it, Y) after every sample."""
+        import torch
+
+        p, nc = _chains(Y, self.n)
+        sample_chains = sample_chains or self._sample_chains
+        assert sample_chains is not None, "run_chains needs sample_chains(W, Y, counter)"
+        keys = _seeds([int(v) ^ 0x5851F42D4C957F2D for v in _seeds(seeds, nc)], nc)
+        if getattr(self, "_W", None) is None or tuple(self._W.shape) != (self.n, nc):
+            self._W = torch.empty((self.n, nc), dtype=torch.float64, device="cuda")
+        for it in range(its):
+            check(lib.pmg_woodbury_noisy_rhs_chains(self._h, nc, keys.ctypes.data, counter0 + it, _ptr(b), _ptr(self._W), _stream()))
+            sample_chains(self._W, Y, counter0 + it)
+            check(lib.pmg_woodbury_correct_chains(self._h, nc, p, _stream()))
+            if callback is not None:
+                callback(it, Y)
         return counter0 + its
 
     def destroy(self):

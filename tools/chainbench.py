@@ -4,7 +4,12 @@
 single-chain entry points.  Builds exactly what bench.py's unstructured_secondary builds: lshape.msh refined 5 times,
 build_hierarchy(A, coarse_max=2000), PMG_COLORING_ITERATED, set_smoother(True, 1.0, 1, 1).
 
-    python tools/chainbench.py [--chains 1 8 32 128] [--its 10] [--regions 5]
+    python tools/chainbench.py [--chains 1 8 32 128] [--its 10] [--regions 5] [--lowrank K]
+
+--lowrank K: posterior lines instead, with K ball observations on the mesh vertices (column j = indicator of the vertices
+within --radius of centre j, divided by their count): the MATLRC sweep (mcgibbs, forward; pmg_mcsor_sample_chains on an
+operator with pmg_mcsor_set_lowrank) and Woodbury + MGMC chains (WoodburySampler.run_chains on the per-chain right-hand-side
+MGMC call), each beside its single-chain entry point (mcsor sample; the WoodburySampler.run loop).
 
 Time per call = median over `regions` event-timed regions of one call of `its` samples each.  Aggregate rate = C * its /
 time.  Roofline fraction = algorithmic bytes (sweep: 12 nnz + 24 N + 16 N C; MGMC: pmg_mgmc_get_algorithmic_bytes_chains)
@@ -44,6 +49,8 @@ def main():
     ap.add_argument("--regions", type=int, default=5)
     ap.add_argument("--refine", type=int, default=5)
     ap.add_argument("--sweep-only", action="store_true", help="only the chains sweep (for counter runs under rocprofv3)")
+    ap.add_argument("--lowrank", type=int, default=0, help="K > 0: the posterior lines with K ball observations")
+    ap.add_argument("--radius", type=float, default=0.1)
     args = ap.parse_args()
 
     import torch
@@ -69,6 +76,8 @@ def main():
 
     b = torch.ones(n, dtype=torch.float64, device="cuda")
     its = args.its
+    if args.lowrank:
+        return lowrank_lines(args, xy, A, mg, b)
     if args.sweep_only:
         for C in args.chains:
             Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
@@ -97,6 +106,67 @@ def main():
                          "vs_single": (C * its * 1e3 / ms_sw) / single["sweep_samples_per_s"]},
                "mgmc": {"chain_samples_per_s": C * its * 1e3 / ms_mg, "ms_per_call": ms_mg, "ms_per_cycle": ms_mg / its, "roofline": alg_mg / (ms_mg / its * 1e-3) / HBM_PEAK,
                         "vs_single": (C * its * 1e3 / ms_mg) / single["mgmc_samples_per_s"]},
+               "finite": bool(torch.isfinite(Y).all().item())}
+        print(json.dumps(rec), flush=True)
+        del Y
+        torch.cuda.empty_cache()
+
+
+def ball_centres(xy, k):
+    """k mesh vertices as ball centres: the three quadrants' midpoints first, then vertices drawn with a fixed seed"""
+    import numpy as np
+
+    fixed = [(0.5, 0.5), (1.5, 0.5), (0.5, 1.5)]
+    if k <= 3:
+        return fixed[:k]
+    rng = np.random.default_rng(0)
+    return fixed + [tuple(xy[i]) for i in rng.choice(len(xy), size=k - 3, replace=False)]
+
+
+def lowrank_lines(args, xy, A, mg, b):
+    import numpy as np
+    import torch
+
+    from parmgmc_amd import COLORING_ITERATED, MCSOR
+    from parmgmc_amd.unstructured import ball_observations
+    from parmgmc_amd.wrappers import WoodburySampler
+
+    n, its, k = A.shape[0], args.its, args.lowrank
+    B = ball_observations(xy, ball_centres(xy, k), args.radius)
+    S = np.linspace(40.0, 80.0, k)
+    mc = MCSOR(A.indptr, A.indices, A.data, COLORING_ITERATED).setup()
+    mc.set_lowrank(B, S)
+    # the Woodbury set-up's solver: ten symmetric Gauss-Seidel sweeps of the prior operator (its quality does not change the timing)
+    gs = MCSOR(A.indptr, A.indices, A.data, COLORING_ITERATED).setup()
+    gs.set_sweep_type(3)
+
+    def solve(rhs, x):
+        for _ in range(10):
+            gs.apply(rhs, x)
+
+    state = {"seed": 0xCAFE, "seeds": None}
+    wb = WoodburySampler(B, S, solve, lambda w, y, ctr: mg.sample(w, y, 1, state["seed"], counter0=ctr),
+                         sample_chains=lambda W, Y, ctr: mg.sample_chains(W, Y, 1, state["seeds"], counter0=ctr))
+    print(json.dumps({"lowrank": k, "support_rows": int((np.abs(B).sum(1) > 0).sum()), "radius": args.radius}), flush=True)
+    y = torch.zeros(n, dtype=torch.float64, device="cuda")
+    ms1_sw = timed(lambda: mc.sample(b, y, its, seed=0xCAFE), args.regions)
+    y.zero_()
+    ms1_wb = timed(lambda: wb.run(b, y, its, 0xCAFE), args.regions)
+    single = {"lowrank_sweep_samples_per_s": its * 1e3 / ms1_sw, "lowrank_sweep_ms": ms1_sw / its,
+              "woodbury_mgmc_samples_per_s": its * 1e3 / ms1_wb, "woodbury_mgmc_ms": ms1_wb / its}
+    print(json.dumps({"single_chain": single}), flush=True)
+    for C in args.chains:
+        seeds = [0xCAFE + 7919 * c for c in range(C)]
+        state["seeds"] = seeds
+        Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+        ms_sw = timed(lambda: mc.sample_chains(b, Y, its, seeds), args.regions)
+        Y.zero_()
+        ms_wb = timed(lambda: wb.run_chains(b, Y, its, seeds), args.regions)
+        rec = {"chains": C, "its": its, "lowrank": k,
+               "lowrank_sweep": {"chain_samples_per_s": C * its * 1e3 / ms_sw, "ms_per_call": ms_sw, "ms_per_sweep": ms_sw / its,
+                                 "vs_single": (C * its * 1e3 / ms_sw) / single["lowrank_sweep_samples_per_s"]},
+               "woodbury_mgmc": {"chain_samples_per_s": C * its * 1e3 / ms_wb, "ms_per_call": ms_wb, "ms_per_sample": ms_wb / its,
+                                 "vs_single": (C * its * 1e3 / ms_wb) / single["woodbury_mgmc_samples_per_s"]},
                "finite": bool(torch.isfinite(Y).all().item())}
         print(json.dumps(rec), flush=True)
         del Y
