@@ -617,6 +617,54 @@ pmg_status pmg_iact(int64_t n, const double *x_host, double *tau, double *acf_ho
    ||C_i - A^-1||_F / ||A^-1||_F with the unbiased covariance over the chains at sample index i */
 pmg_status pmg_estimate_covariance_errors(int32_t n, const int32_t *rowptr_host, const int32_t *colidx_host, const double *vals_host, int32_t chains, int32_t samples_per_chain, const double *samples_host, double *errs_host);
 
+/* ---- chain statistics on the device: what the drivers do with their chains ------------------------------------ */
+/* The consumer of pmg_*_sample_chains: running mean and variance of every row over all samples (MS_ComputeMeanAndVar,
+   src/ms.c:221-251; the benchmark's Welford loop, examples/benchmark/main.cc:151-175), the scalar quantities of interest of
+   every chain per step (the sample callback of examples/ex7.c:40-52) and the Gelman-Rubin R-hat on them (ex7.c:61-93), without
+   a sample leaving the device.  One kernel reads a step's Y (n x nchains, chain fastest, natural rows: what
+   pmg_*_sample_chains write and pmg_chains_callback receives) exactly once.
+   Arithmetic per row, with running (N, mean, M2) and a step's y_0 .. y_{C-1}:
+       bm  = (sum_c y_c) / C;   bM2 = sum_c (y_c - bm)^2          (second pass over registers, no sum of squares)
+       d   = bm - mean;  N' = N + C
+       mean += d * C / N';   M2 += bM2 + d * d * N * C / N';   N = N';      var = M2 / (N - 1)
+   (Chan/Golub/LeVeque pairwise merge; Welford's update for C = 1; for C > 64 the step's (bm, bM2) is itself the merge, by the
+   same formula, of chunks of 64 chains in chunk order).  QOI: t[q][step][c] = sum_r w_q[r] * Y[r, c].  The order of every sum
+   is a function of (n, nchains) alone (stated in kernels_chainstats.hip and DESIGN 11.2): it does not depend on the stream or
+   on earlier calls, there are no floating-point atomics, and two runs give the same bits.
+   Creation and all argument checks touch no device; device memory is allocated by the first update.  At most
+   PMG_CHAINSTATS_MAX_QOI quantities of interest per handle. */
+#define PMG_CHAINSTATS_MAX_QOI 4
+typedef struct pmg_chainstats_s *pmg_chainstats;
+/* PMG_ERR_ARG_OUTOFRANGE: n < 1, nchains < 1 (nchains = 1 serves the single-chain samplers), nqoi outside
+   [0, PMG_CHAINSTATS_MAX_QOI], max_steps < 1 (max_steps sizes the trace: nqoi x max_steps x nchains doubles on the device) */
+pmg_status pmg_chainstats_create(int32_t n, int32_t nchains, int32_t nqoi, int32_t max_steps, pmg_chainstats *cs);
+pmg_status pmg_chainstats_destroy(pmg_chainstats *cs);
+/* weights of QOI q: n host doubles (copied; VecDot with meas_vec, ex7.c:45), or NULL for all ones (VecSum, ex7.c:46; the
+   default, reads no weights).  Takes effect at the next update. */
+pmg_status pmg_chainstats_set_qoi(pmg_chainstats cs, int32_t q, const double *w_host);
+/* the stream the two callbacks below launch on (they carry none): the one the sampler is called with */
+pmg_status pmg_chainstats_set_stream(pmg_chainstats cs, void *stream);
+/* one step of all chains.  PMG_ERR_ARG_OUTOFRANGE once max_steps updates have been made since creation or the last reset. */
+pmg_status pmg_chainstats_update(pmg_chainstats cs, const double *Y_dev, void *stream);
+/* ready-made callbacks, ctx = the handle: pass them to pmg_mgmc_sample_chains / pmg_mgmc_sample (the latter needs nchains = 1).
+   PMG_ERR_ARG_SIZ when the sampler's sizes are not the handle's. */
+int pmg_chainstats_callback(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
+int pmg_chainstats_sample_callback(int32_t it, const double *y_nat_dev, int32_t n, void *ctx);
+/* forget everything (the end of burn-in); waits for updates in flight */
+pmg_status pmg_chainstats_reset(pmg_chainstats cs);
+pmg_status pmg_chainstats_get_count(pmg_chainstats cs, int32_t *steps, int64_t *samples); /* samples = steps * nchains */
+/* mean and unbiased variance of every row over all samples seen (n device doubles each; one of them may be NULL).
+   PMG_ERR_ARG_WRONGSTATE with fewer than two samples (src/ms.c:233). */
+pmg_status pmg_chainstats_get_fields(pmg_chainstats cs, double *mean_dev, double *var_dev, void *stream);
+/* QOI q of steps [first, first + count) as count x nchains host doubles, step-major.  Synchronises the device.
+   PMG_ERR_ARG_OUTOFRANGE: q or the window outside what has been recorded. */
+pmg_status pmg_chainstats_get_trace(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, double *vals_host);
+/* GelmanRubin (examples/ex7.c:61-93) term by term in its order, host arithmetic: vals_host[i * n + j] = value j of chain i
+   (the reference's vals[i][j]).  PMG_ERR_ARG_OUTOFRANGE: fewer than 2 chains or 2 values. */
+pmg_status pmg_gelman_rubin(int32_t chains, int64_t n, const double *vals_host, double *gr);
+/* the same on steps [first, first + count) of the trace of QOI q */
+pmg_status pmg_chainstats_rhat(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, double *gr);
+
 /* ------------------------------------------------------------------------------------------------------ */
 /* The registration boundary without PETSc: PCRegister / PCSetType / pc->ops / PCSetSampleCallback /        */
 /* PCSHELL / KSPRICHARDSON on raw device arrays (reference src/parmgmc.c:44-54,118-151; examples/ex1.c,     */

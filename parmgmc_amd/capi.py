@@ -273,6 +273,19 @@ _sig = {
     "pmg_mgmc_sample_chains_rhs": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _int, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
     "pmg_woodbury_noisy_rhs_chains": (_int, [_vp, _i32, _vp, _u64, _vp, _vp, _vp]),
     "pmg_woodbury_correct_chains": (_int, [_vp, _i32, _vp, _vp]),
+    "pmg_chainstats_create": (_int, [_i32, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pmg_chainstats_destroy": (_int, [C.POINTER(_vp)]),
+    "pmg_chainstats_set_qoi": (_int, [_vp, _i32, _vp]),
+    "pmg_chainstats_set_stream": (_int, [_vp, _vp]),
+    "pmg_chainstats_update": (_int, [_vp, _vp, _vp]),
+    "pmg_chainstats_callback": (_int, [_i32, _vp, _i32, _i32, _vp]),
+    "pmg_chainstats_sample_callback": (_int, [_i32, _vp, _i32, _vp]),
+    "pmg_chainstats_reset": (_int, [_vp]),
+    "pmg_chainstats_get_count": (_int, [_vp, C.POINTER(_i32), C.POINTER(_i64)]),
+    "pmg_chainstats_get_fields": (_int, [_vp, _vp, _vp, _vp]),
+    "pmg_chainstats_get_trace": (_int, [_vp, _i32, _i32, _i32, _vp]),
+    "pmg_gelman_rubin": (_int, [_i32, _i64, _vp, C.POINTER(_dbl)]),
+    "pmg_chainstats_rhat": (_int, [_vp, _i32, _i32, _i32, C.POINTER(_dbl)]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

@@ -205,6 +205,17 @@ int pmgk_lrc_btx_chains(int64_t n, const int64_t *rows, int k, const double *M, 
 int pmgk_lrc_axpy_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, void *stream);
 int pmgk_lrc_noise_chains(int k, int32_t nchains, const uint64_t *keys, uint64_t tag, uint64_t sweep, const double *sqrtS, double *eta, void *stream);
 
+/* running statistics of the chains (kernels_chainstats.hip): one pass over a step's n x C array Y (chain fastest) merges its C
+   samples per row into the running (mean, M2) and forms the nqoi weighted column sums w_q . Y[:, c]; every sum in an order that
+   (n, C) alone fixes (the kernel file states it).  w[q] == NULL: all ones, no weights read. */
+#define PMGK_CHAINSTATS_MAX_QOI 4
+typedef struct {
+  const double *w[PMGK_CHAINSTATS_MAX_QOI];
+} pmgk_chainstats_qoi;
+void pmgk_chainstats_geometry(int64_t n, int32_t nchains, int32_t *iters, int32_t *nblocks);
+int  pmgk_chainstats_update(int64_t n, int32_t nchains, int nqoi, const pmgk_chainstats_qoi *Q, double count, const double *Y, double *mean, double *M2, double *partial, double *trace_step, int64_t qstride, void *stream);
+int  pmgk_chainstats_fields(int64_t n, double count, const double *mean, const double *M2, double *mean_out, double *var_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

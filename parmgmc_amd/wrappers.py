@@ -115,7 +115,8 @@ class MCSOR:
 
     def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, scaled: bool = True) -> int:
         """`its` samples of C chains; column c equals sample(b, Y[:, c], its, seeds[c], counter0, scaled) bit for bit.  b: one
-        vector (n,) shared by the chains, or one right-hand side per chain (n, C), column c = b[:, c]"""
+        vector (n,) shared by the chains, or one right-hand side per chain (n, C), column c = b[:, c].  The C entry point has no
+        callback: for running statistics call ChainStats.update(Y) between calls (sample_chains(b, Y, 1, seeds, counter0 + it))."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
@@ -431,8 +432,15 @@ class MGMC:
     def level_lowrank_residual_sub(self, level: int, x, out, restricted: bool = False):
         check(lib.pmg_mgmc_level_lowrank_residual_sub(self._h, level, int(restricted), _ptr(x), _ptr(out), _stream()))
 
-    def sample(self, b, y, its: int, seed: int, counter0: int = 0, guesszero: bool = False, callback=None) -> int:
+    def sample(self, b, y, its: int, seed: int, counter0: int = 0, guesszero: bool = False, callback=None, stats=None) -> int:
+        """stats: a ChainStats of one chain, updated after every sample by the library's own callback (no Python in the loop)"""
         out = C.c_uint64()
+        if stats is not None:
+            if callback is not None:
+                raise ValueError("stats= and callback= exclude each other")
+            cb, ctx = stats._as_callback(self.n, 1, lib.pmg_chainstats_sample_callback)
+            check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, ctx, _stream()))
+            return out.value
         if callback is None:
             cb = None
         else:
@@ -452,14 +460,19 @@ class MGMC:
         check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, None, _stream()))
         return out.value
 
-    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None) -> int:
+    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None, stats=None) -> int:
         """`its` samples of C chains on a hierarchy from from_hierarchy: Y is a contiguous (n, C) float64 tensor, b one vector
         (n,) shared by all chains or one per chain (n, C); column c equals sample(b or b[:, c], Y[:, c], its, seeds[c], ...) bit
-        for bit.  callback(it, Y) after every sample; a raised exception aborts the loop."""
+        for bit.  callback(it, Y) after every sample; a raised exception aborts the loop.  stats: a ChainStats(n, C) updated
+        after every sample by the library's own callback instead (no Python in the loop; excludes callback)."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
-        cb = None
+        cb, ctx = None, None
+        if stats is not None:
+            if callback is not None:
+                raise ValueError("stats= and callback= exclude each other")
+            cb, ctx = stats._as_callback(self.n, nc, lib.pmg_chainstats_callback)
         if callback is not None:
 
             def _cb(it, ptr, n, nchains, _ctx):
@@ -474,7 +487,7 @@ class MGMC:
 
             cb = capi.CHAINS_CALLBACK(_cb)
         fn = lib.pmg_mgmc_sample_chains_rhs if _per_chain_rhs(b, self.n, nc) else lib.pmg_mgmc_sample_chains
-        check(fn(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(guesszero), counter0, C.byref(out), cb, None, _stream()))
+        check(fn(self._h, nc, s.ctypes.data, _ptr(b), p, its, int(guesszero), counter0, C.byref(out), cb, ctx, _stream()))
         return out.value
 
     def algorithmic_bytes_chains(self, nchains: int):
@@ -540,13 +553,15 @@ class WoodburySampler:
                 callback(it, y)
         return counter0 + its
 
-    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None) -> int:
+    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None, stats=None) -> int:
         """run() on C chains of one device: Y is a contiguous (n, C) float64 tensor, b one vector (n,) shared by the chains;
         column c equals run(b, Y[:, c], its, seeds[c], counter0) bit for bit when sample_chains(W, Y, counter) advances every
         column c of Y as sample(W[:, c], Y[:, c], counter) does -- e.g. MGMC.sample_chains with per-chain right-hand sides.
-        callback(it, Y) after every sample."""
+        callback(it, Y) after every sample, or stats.update(Y) for a ChainStats(n, C) (not both)."""
         import torch
 
+        if stats is not None and callback is not None:
+            raise ValueError("stats= and callback= exclude each other")
         p, nc = _chains(Y, self.n)
         sample_chains = sample_chains or self._sample_chains
         assert sample_chains is not None, "run_chains needs sample_chains(W, Y, counter)"
@@ -557,6 +572,8 @@ class WoodburySampler:
             check(lib.pmg_woodbury_noisy_rhs_chains(self._h, nc, keys.ctypes.data, counter0 + it, _ptr(b), _ptr(self._W), _stream()))
             sample_chains(self._W, Y, counter0 + it)
             check(lib.pmg_woodbury_correct_chains(self._h, nc, p, _stream()))
+            if stats is not None:
+                stats.update(Y)
             if callback is not None:
                 callback(it, Y)
         return counter0 + its
@@ -570,6 +587,98 @@ class WoodburySampler:
             self.destroy()
         except Exception:
             pass
+
+
+class ChainStats:
+    """pmg_chainstats: running mean and variance of every row over all steps x chains samples, the quantities of interest
+    w_q . Y[:, c] of every chain per step and R-hat on them, kept on the device (replaces the host loops of the reference's
+    examples/ex7.c:40-93, src/ms.c:221-251 and examples/benchmark/main.cc:151-175).
+      qois: a list with one entry per QOI -- None for all ones (VecSum) or n weights (VecDot); at most 4 entries."""
+
+    def __init__(self, n: int, nchains: int = 1, qois=(), max_steps: int = 1000):
+        qois = list(qois)
+        self.n, self.nchains, self.nqoi, self.max_steps = int(n), int(nchains), len(qois), int(max_steps)
+        self._h = C.c_void_p()
+        check(lib.pmg_chainstats_create(self.n, self.nchains, self.nqoi, self.max_steps, C.byref(self._h)))
+        for q, w in enumerate(qois):
+            self.set_qoi(q, w)
+
+    def set_qoi(self, q: int, w=None):
+        if w is None:
+            check(lib.pmg_chainstats_set_qoi(self._h, q, None))
+            return
+        w = np.ascontiguousarray(w.detach().cpu().numpy() if hasattr(w, "detach") else w, np.float64)
+        assert w.shape == (self.n,), f"need {self.n} weights"
+        check(lib.pmg_chainstats_set_qoi(self._h, q, w.ctypes.data))
+
+    def update(self, Y):
+        """one step: Y is a contiguous (n, C) float64 CUDA tensor (or (n,) for one chain), on the current stream"""
+        assert Y.numel() == self.n * self.nchains and (Y.dim() == 1 or tuple(Y.shape) == (self.n, self.nchains)), f"need an ({self.n}, {self.nchains}) tensor"
+        check(lib.pmg_chainstats_update(self._h, _ptr(Y), _stream()))
+
+    def _as_callback(self, n: int, nchains: int, fn):
+        """(function pointer, context) for a sampler's callback argument; the callback launches on the current stream"""
+        assert (n, nchains) == (self.n, self.nchains), f"ChainStats of {self.n} x {self.nchains} on samples of {n} x {nchains}"
+        check(lib.pmg_chainstats_set_stream(self._h, _stream()))
+        return C.cast(fn, C.c_void_p), self._h
+
+    def reset(self):
+        check(lib.pmg_chainstats_reset(self._h))
+
+    def count(self):
+        """(steps, samples = steps * chains)"""
+        st, sm = C.c_int32(), C.c_int64()
+        check(lib.pmg_chainstats_get_count(self._h, C.byref(st), C.byref(sm)))
+        return st.value, sm.value
+
+    def fields(self):
+        """(mean, var): device tensors of n entries, the unbiased variance over all samples seen"""
+        import torch
+
+        mean = torch.empty(self.n, dtype=torch.float64, device="cuda")
+        var = torch.empty(self.n, dtype=torch.float64, device="cuda")
+        check(lib.pmg_chainstats_get_fields(self._h, _ptr(mean), _ptr(var), _stream()))
+        return mean, var
+
+    def trace(self, q: int = 0, first: int = 0, count=None) -> np.ndarray:
+        """QOI q of the steps [first, first + count) as a host array (count, C); count = None: all recorded steps from first"""
+        if count is None:
+            count = max(self.count()[0] - first, 0)
+        out = np.empty((max(count, 0), self.nchains))
+        check(lib.pmg_chainstats_get_trace(self._h, q, first, count, out.ctypes.data))
+        return out
+
+    def rhat(self, q: int = 0, first: int = 0, count=None) -> float:
+        """Gelman-Rubin R-hat (examples/ex7.c:61-93) of QOI q over the steps [first, first + count)"""
+        if count is None:
+            count = max(self.count()[0] - first, 0)
+        gr = C.c_double()
+        check(lib.pmg_chainstats_rhat(self._h, q, first, count, C.byref(gr)))
+        return gr.value
+
+    def iact(self, q: int = 0, first: int = 0, count=None):
+        """pmg_iact of every chain's trace of QOI q: a list of (tau, valid), one per chain"""
+        t = self.trace(q, first, count)
+        return [iact(t[:, c]) for c in range(self.nchains)]
+
+    def destroy(self):
+        if self._h:
+            check(lib.pmg_chainstats_destroy(C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def gelman_rubin(vals) -> float:
+    """GelmanRubin (reference examples/ex7.c:61-93): vals is (chains, n), host arithmetic in the reference's order"""
+    v = np.ascontiguousarray(vals, np.float64)
+    assert v.ndim == 2
+    gr = C.c_double()
+    check(lib.pmg_gelman_rubin(v.shape[0], v.shape[1], v.ctypes.data, C.byref(gr)))
+    return gr.value
 
 
 def vec_set_random_standard_normal(x, seed: int, counter: int = 0):

@@ -6,6 +6,11 @@ build_hierarchy(A, coarse_max=2000), PMG_COLORING_ITERATED, set_smoother(True, 1
 
     python tools/chainbench.py [--chains 1 8 32 128] [--its 10] [--regions 5] [--lowrank K]
 
+--stats: the chain statistics instead (pmg_chainstats_update, nqoi = 1 with weights): time per update on an (n, C) array,
+algorithmic bytes 8 n C + 32 n + 8 n nqoi over that time, beside the read-2/write-1 triad (pmg_stream_triad on 4 n C / 3 doubles,
+timed here in the same run) and beside the torch formulation of the same step (s = Y.sum(1); q = ((Y - (s/C)[:, None])**2).sum(1);
+t = w @ Y; the merge on n-vectors); then MGMC chains with and without stats= (the added time per sample beside the update time).
+
 --lowrank K: posterior lines instead, with K ball observations on the mesh vertices (column j = indicator of the vertices
 within --radius of centre j, divided by their count): the MATLRC sweep (mcgibbs, forward; pmg_mcsor_sample_chains on an
 operator with pmg_mcsor_set_lowrank) and Woodbury + MGMC chains (WoodburySampler.run_chains on the per-chain right-hand-side
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--sweep-only", action="store_true", help="only the chains sweep (for counter runs under rocprofv3)")
     ap.add_argument("--lowrank", type=int, default=0, help="K > 0: the posterior lines with K ball observations")
     ap.add_argument("--radius", type=float, default=0.1)
+    ap.add_argument("--stats", action="store_true", help="the chain-statistics lines (pmg_chainstats_update)")
     args = ap.parse_args()
 
     import torch
@@ -76,6 +82,8 @@ def main():
 
     b = torch.ones(n, dtype=torch.float64, device="cuda")
     its = args.its
+    if args.stats:
+        return stats_lines(args, n, mg, b)
     if args.lowrank:
         return lowrank_lines(args, xy, A, mg, b)
     if args.sweep_only:
@@ -109,6 +117,93 @@ def main():
                "finite": bool(torch.isfinite(Y).all().item())}
         print(json.dumps(rec), flush=True)
         del Y
+        torch.cuda.empty_cache()
+
+
+def timed_all(fn, regions):
+    """timed() that also returns the spread: (median, min, max) in ms"""
+    import torch
+
+    fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(regions):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    ms.sort()
+    return ms[len(ms) // 2], ms[0], ms[-1]
+
+
+def stats_lines(args, n, mg, b):
+    import torch
+
+    from parmgmc_amd import ChainStats
+    from parmgmc_amd.capi import check, lib
+
+    reps, nqoi = 20, 1
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    w = torch.randn(n, dtype=torch.float64, device="cuda", generator=gen)
+    for C in args.chains:
+        Y = torch.randn((n, C), dtype=torch.float64, device="cuda", generator=gen)
+        cs = ChainStats(n, C, [w], max_steps=reps * (args.regions + 1))
+
+        def fused():
+            for _ in range(reps):
+                cs.update(Y)
+
+        ms_f = timed(fused, args.regions) / reps
+        alg = 8.0 * n * C + 32.0 * n + 8.0 * n * nqoi
+        # the triad on the same number of bytes: 24 bytes per entry
+        nt = int(alg / 24.0) & ~1
+        a3, b3, c3 = (torch.zeros(nt, dtype=torch.float64, device="cuda") for _ in range(3))
+        st = torch.cuda.current_stream().cuda_stream
+
+        def triad():
+            for _ in range(reps):
+                check(lib.pmg_stream_triad(nt, a3.data_ptr(), b3.data_ptr(), c3.data_ptr(), st))
+
+        ms_t = timed(triad, args.regions) / reps
+        del a3, b3, c3
+        # what a caller writes today: three passes over Y and the merge on n-vectors
+        state = {"N": 0.0, "mean": torch.zeros(n, dtype=torch.float64, device="cuda"), "M2": torch.zeros(n, dtype=torch.float64, device="cuda")}
+
+        def torch_step():
+            for _ in range(reps):
+                s = Y.sum(1)
+                bm = s / C
+                q = ((Y - bm[:, None]) ** 2).sum(1)
+                t = w @ Y  # noqa: F841
+                N1 = state["N"] + C
+                d = bm - state["mean"]
+                state["mean"] = state["mean"] + d * (C / N1)
+                state["M2"] = state["M2"] + q + d * d * (state["N"] * C / N1)
+                state["N"] = N1
+
+        ms_p = timed(torch_step, args.regions) / reps
+        rec = {"chains": C, "nqoi": nqoi, "update_us": ms_f * 1e3, "algorithmic_bytes": alg, "update_GBps": alg / ms_f / 1e6, "triad_us_same_bytes": ms_t * 1e3, "triad_GBps": 24.0 * nt / ms_t / 1e6,
+               "update_over_triad_bandwidth": (alg / ms_f) / (24.0 * nt / ms_t), "torch_us": ms_p * 1e3, "torch_over_fused": ms_p / ms_f}
+        print(json.dumps(rec), flush=True)
+        del Y, cs, state
+        torch.cuda.empty_cache()
+    # MGMC chains with and without stats=
+    its = args.its
+    for C in args.chains:
+        if C < 2:
+            continue
+        seeds = [0xCAFE + 7919 * c for c in range(C)]
+        Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+        cs = ChainStats(n, C, [w], max_steps=its * (args.regions + 1))
+        plain = timed_all(lambda: mg.sample_chains(b, Y, its, seeds), args.regions)
+        with_stats = timed_all(lambda: mg.sample_chains(b, Y, its, seeds, stats=cs), args.regions)
+        # a callback alone makes the sampler write the natural-order copy after every sample: the fair baseline of the difference
+        print(json.dumps({"chains": C, "its": its, "mgmc_ms_per_sample": plain[0] / its, "mgmc_spread_ms_per_sample": [plain[1] / its, plain[2] / its],
+                          "mgmc_stats_ms_per_sample": with_stats[0] / its, "mgmc_stats_spread_ms_per_sample": [with_stats[1] / its, with_stats[2] / its],
+                          "added_us_per_sample": (with_stats[0] - plain[0]) / its * 1e3, "steps_recorded": cs.count()[0]}), flush=True)
+        del Y, cs
         torch.cuda.empty_cache()
 
 
