@@ -628,42 +628,41 @@ pmg_status pmg_mgmc_set_keep_host(pmg_mgmc h, int keep)
   return PMG_SUCCESS;
 }
 
+/* the process-wide switches that choose a level's kernels inside the cycle: each is read here and nowhere else, once per
+   process, at its first use */
+static int env_int(const char *e, int dflt) { return e ? atoi(e) : dflt; }
+static int sw_st27_pair(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_ST27_PAIR"), 1); return v; }
+static int sw_st27_pair_slab(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_ST27_PAIR_SLAB"), 1); return v; } /* probes: 2 = paired residual only, 3 = paired sweeps only */
+static int sw_prolong_both(void) { static int v = -1; if (v < 0) v = getenv("PMG_MG_PROLONG_BOTH") != NULL; return v; }
+static int sw_fused_zero(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_MG_FUSED_ZERO"), 1); return v; }
+
 /* the phase-fused out-of-place sweep and the paired residual (kernels_stencil27_pair.hip) serve class-stencil levels
    that live on one device; PMG_ST27_PAIR=0 keeps the one-launch-per-colour kernels (same bits) */
-static int st27_use_pair(const mg_level *Lv)
-{
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("PMG_ST27_PAIR");
-    env           = e ? atoi(e) : 1;
-  }
-  return env && Lv->is_st27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz;
-}
+static int st27_use_pair(const mg_level *Lv) { return sw_st27_pair() && Lv->is_st27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz; }
 
 /* the same kernels on the z-slab of a distributed class-stencil level: one launch per z-parity phase instead of four, the
    halo of the boundary planes behind each as before; PMG_ST27_PAIR_SLAB=0 keeps the per-colour kernels (same bits) */
-static int st27_use_pair_slab(const mg_level *Lv)
-{
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("PMG_ST27_PAIR_SLAB");
-    env           = e ? atoi(e) : 1;
-  }
-  return env && Lv->is_st27 && Lv->distributed;
-}
-static int st27_pair_slab_mode(void) { const char *e = getenv("PMG_ST27_PAIR_SLAB"); return e ? atoi(e) : 1; } /* probe: 2 = residual only, 3 = sweeps only */
+static int st27_use_pair_slab(const mg_level *Lv) { return sw_st27_pair_slab() && Lv->is_st27 && Lv->distributed; }
+
+/* the level's own iterate is swept out of place, into Lv->x2 */
+static int st27_out_of_place(const mg_level *Lv) { return Lv->x2 && st27_use_pair(Lv); }
 
 /* one directional sweep of a class-stencil level on (b, *x): in place, or out of place into Lv->x2 followed by a swap of
    the two buffers when x is the level's own iterate */
+static void st27_swap(mg_level *Lv)
+{
+  double *t = Lv->x;
+  Lv->x     = Lv->x2;
+  Lv->x2    = t;
+}
+
 static pmg_status st27_one_sweep(mg_level *Lv, const pmgk_st27 *S, int backward, double omega, int noisy, uint64_t seed, uint64_t sweep, const double *b, int x_is_zero, void *stream)
 {
-  if (Lv->x2 && st27_use_pair(Lv)) {
+  if (st27_out_of_place(Lv)) {
     /* x_is_zero: the iterate is the zero vector and has NOT been stored (level_iterate_is_unset): the sweep neither reads it
        nor needs the memset */
     PMG_KERNEL(pmgk_st27_sweep_pp(S, backward, omega, noisy, seed, sweep, b, x_is_zero ? NULL : Lv->x, Lv->x2, stream));
-    double *t = Lv->x;
-    Lv->x     = Lv->x2;
-    Lv->x2    = t;
+    st27_swap(Lv);
     return PMG_SUCCESS;
   }
   PMG_KERNEL(pmgk_st27_sweep(S, backward, omega, noisy, seed, sweep, b, Lv->x, stream));
@@ -795,7 +794,6 @@ static pmg_status upload_transfer(const hcsr *M, const int32_t *rowpos_of, const
   return st;
 }
 
-static pmg_status upload_transfer(const hcsr *M, const int32_t *rowpos_of, const int32_t *colpos_of, int32_t **rowpos, int32_t **rowptr, int32_t **col, double **val);
 static int        st27_from_csr(mg_level *Lv, const hcsr *A, double omega, pmg_status *st);
 static pmg_status stencil_tables_from_proxy(pmg_mgmc h, st27_table *tab, int *ok);
 static pmg_status mgmc_setup_stencil(pmg_mgmc h, const st27_table *tab);
@@ -1536,41 +1534,55 @@ static pmg_status halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stream)
   return pmg_dist_exchange(h->dist, nseg, slo, n, rlo, n, shi, n, rhi, n, stream);
 }
 
-/* `its` samples of the level sampler on a class-stencil level (same draw numbering as pmg_mcsor_sample_layout); on a
-   z-slab the two z-parity phases of a sweep are separated by a halo of the boundary planes */
-static pmg_status st27_sample(pmg_mgmc h, mg_level *Lv, int its, uint64_t seed, uint64_t *ctr, void *stream)
+/* `its` samples of a level sampler whose low-rank update is applied around the sweeps HERE (class-stencil levels, the grid
+   level of a z-slab hierarchy): noise term, directional sweep (the part that differs), repair, halo */
+typedef pmg_status (*mg_dir_sweep)(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream);
+
+static pmg_status mg_lowrank_sweeps(pmg_mgmc h, mg_level *Lv, int its, mg_dir_sweep sweep, uint64_t seed, uint64_t *ctr, void *stream)
 {
-  pmgk_st27 S = Lv->st;
-  S.sqrtdiag  = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;
-  for (int it = 0; it < its; ++it) {
-    const int ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+  const int ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+  for (int it = 0; it < its; ++it)
     for (int d = 0; d < ndir; ++d) {
-      const int     backward = ndir == 2 ? d : h->sweep_type == PMG_SOR_BACKWARD_SWEEP;
-      const double *rhs      = Lv->b;
+      const int     dir = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : h->sweep_type;
+      const double *rhs = Lv->b;
       if (Lv->lrc) PMG_CALL(pmg_lrc_rhs(Lv->lrc, Lv->b, seed, *ctr, &rhs, stream)); /* + B (sqrt(S) o eta), src/pc_mcgibbs.c:130-140 */
-      if (Lv->distributed && Lv->x2 && st27_use_pair_slab(Lv) && st27_pair_slab_mode() != 2) { /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
-        PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, 0, h->omega, 1, seed, *ctr, rhs, Lv->x, Lv->x2, stream));
-        PMG_CALL(halo_level(h, Lv, Lv->x2, stream));
-        PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, 1, h->omega, 1, seed, (*ctr)++, rhs, Lv->x, Lv->x2, stream));
-        PMG_CALL(halo_level(h, Lv, Lv->x2, stream));
-        double *t = Lv->x;
-        Lv->x     = Lv->x2;
-        Lv->x2    = t;
-      } else if (Lv->distributed) {
-        PMG_KERNEL(pmgk_st27_sweep_phase(&S, backward, 0, h->omega, 1, seed, *ctr, rhs, Lv->x, stream));
-        PMG_CALL(halo_level(h, Lv, Lv->x, stream));
-        PMG_KERNEL(pmgk_st27_sweep_phase(&S, backward, 1, h->omega, 1, seed, (*ctr)++, rhs, Lv->x, stream));
-        PMG_CALL(halo_level(h, Lv, Lv->x, stream));
-      } else {
-        PMG_CALL(st27_one_sweep(Lv, &S, backward, h->omega, 1, seed, (*ctr)++, rhs, Lv->x_unset, stream));
-        Lv->x_unset = 0;
-      }
-      if (Lv->lrc) PMG_CALL(pmg_lrc_rhs_done(Lv->lrc, stream));
-      if (Lv->lrc) PMG_CALL(pmg_lrc_post(Lv->lrc, backward ? PMG_SOR_BACKWARD_SWEEP : PMG_SOR_FORWARD_SWEEP, Lv->x, stream)); /* src/mc_sor.c:101-112 */
-      if (Lv->lrc && Lv->distributed) PMG_CALL(halo_level(h, Lv, Lv->x, stream)); /* the repair changed boundary planes */
+      PMG_CALL(sweep(h, Lv, dir, rhs, seed, ctr, stream));
+      if (!Lv->lrc) continue;
+      PMG_CALL(pmg_lrc_rhs_done(Lv->lrc, stream));
+      PMG_CALL(pmg_lrc_post(Lv->lrc, dir, Lv->x, stream)); /* src/mc_sor.c:101-112 */
+      PMG_CALL(halo_level(h, Lv, Lv->x, stream));          /* the repair changed boundary planes */
     }
-  }
   return PMG_SUCCESS;
+}
+
+/* class-stencil level (same draw numbering as pmg_mcsor_sample_layout); on a z-slab the two z-parity phases of a sweep are
+   separated by a halo of the boundary planes */
+static pmg_status st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream)
+{
+  const int backward = dir == PMG_SOR_BACKWARD_SWEEP;
+  pmgk_st27 S        = Lv->st;
+  S.sqrtdiag         = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;
+  if (!Lv->distributed) {
+    PMG_CALL(st27_one_sweep(Lv, &S, backward, h->omega, 1, seed, (*ctr)++, rhs, Lv->x_unset, stream));
+    Lv->x_unset = 0;
+    return PMG_SUCCESS;
+  }
+  const int pp  = Lv->x2 && st27_use_pair_slab(Lv) && sw_st27_pair_slab() != 2; /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
+  double   *out = pp ? Lv->x2 : Lv->x;
+  for (int phase = 0; phase < 2; ++phase) {
+    if (pp) PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, phase, h->omega, 1, seed, *ctr, rhs, Lv->x, out, stream));
+    else PMG_KERNEL(pmgk_st27_sweep_phase(&S, backward, phase, h->omega, 1, seed, *ctr, rhs, out, stream));
+    PMG_CALL(halo_level(h, Lv, out, stream));
+  }
+  ++*ctr;
+  if (pp) st27_swap(Lv);
+  return PMG_SUCCESS;
+}
+
+/* grid level of a z-slab hierarchy: one slab sweep (leaves the ghost planes current) */
+static pmg_status slab_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream)
+{
+  return pmg_dist_sample_cvec(h->dist, rhs, Lv->x, 1, h->scaled, dir, seed, *ctr, ctr, stream);
 }
 
 /* per-level noise seed: levels draw from independent streams */
@@ -1579,25 +1591,48 @@ static uint64_t level_seed(uint64_t seed, int level) { return seed + 0x9E3779B97
 static pmg_status mg_smooth(pmg_mgmc h, int l, uint64_t seed, uint64_t *ctr, void *stream)
 {
   mg_level *Lv = &h->lv[l];
-  if (Lv->is_grid && h->dist && Lv->lrc) { /* MATLRC on z-slabs: noise term, one slab sweep, repair, per directional sweep */
-    for (int it = 0; it < h->nu; ++it) {
-      const int ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-      for (int d = 0; d < ndir; ++d) {
-        const int     dir = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : h->sweep_type;
-        const double *rhs = Lv->b;
-        PMG_CALL(pmg_lrc_rhs(Lv->lrc, Lv->b, level_seed(seed, l), *ctr, &rhs, stream));
-        PMG_CALL(pmg_dist_sample_cvec(h->dist, rhs, Lv->x, 1, h->scaled, dir, level_seed(seed, l), *ctr, ctr, stream));
-        PMG_CALL(pmg_lrc_rhs_done(Lv->lrc, stream));
-        PMG_CALL(pmg_lrc_post(Lv->lrc, dir, Lv->x, stream));
-        PMG_CALL(halo_level(h, Lv, Lv->x, stream)); /* the repair changed boundary planes */
-      }
-    }
-  } else if (Lv->is_grid && h->dist) PMG_CALL(pmg_dist_sample_cvec(h->dist, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* leaves the ghost planes current */
+  if (Lv->is_grid && h->dist && Lv->lrc) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, slab_dir_sweep, level_seed(seed, l), ctr, stream)); /* MATLRC on z-slabs */
+  else if (Lv->is_grid && h->dist) PMG_CALL(pmg_dist_sample_cvec(h->dist, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* leaves the ghost planes current */
   else if (Lv->is_grid) PMG_CALL(pmg_grid_sample_cvec(Lv->g, Lv->b, Lv->x, h->nu, h->scaled, level_seed(seed, l), *ctr, ctr, stream));
-  else if (Lv->is_st27) PMG_CALL(st27_sample(h, Lv, h->nu, level_seed(seed, l), ctr, stream));
+  else if (Lv->is_st27) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, st27_dir_sweep, level_seed(seed, l), ctr, stream));
   else if (Lv->dm) PMG_CALL(pmg_distmcsor_sample_layout(Lv->dm, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* row block: refreshes the ghost rows first, leaves them current */
   else PMG_CALL(pmg_mcsor_sample_layout(Lv->mc, Lv->b, Lv->x, h->nu, h->scaled, level_seed(seed, l), *ctr, ctr, stream));
   return PMG_SUCCESS;
+}
+
+/* r = b - A_l x by the level's residual kernel; the low-rank term of an update the LEVEL holds is the caller's */
+static pmg_status mg_residual(mg_level *Lv, int pair, const double *b, const double *x, double *r, void *stream)
+{
+  if (Lv->is_grid) return pmg_grid_residual_cvec(Lv->g, b, x, r, stream);
+  if (Lv->is_st27 && pair) PMG_KERNEL(pmgk_st27_residual_pair(&Lv->st, b, x, r, stream));
+  else if (Lv->is_st27) PMG_KERNEL(pmgk_st27_residual(&Lv->st, b, x, r, stream));
+  else if (Lv->dm) return pmg_distmcsor_residual_layout(Lv->dm, b, x, r, stream); /* row block: + the all-reduced low-rank term */
+  else return pmg_mcsor_residual_layout(Lv->mc, b, x, r, stream);
+  return PMG_SUCCESS;
+}
+
+/* Level l distributed, level l - 1 replicated (the fold): a rank restricts into the coarse planes it owns -- CD becomes
+   those planes, the vector is returned shifted to them (plane K of the full-size vector = plane K - kz0 of the shifted
+   one) -- and an all-gather of the planes completes the vector on every rank */
+static double *fold_own_planes(pmg_mgmc h, int l, pmgk_st27_dims *CD, double *b_coarse)
+{
+  const int32_t *cc = h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1);
+  CD->kz0           = cc[h->rank];
+  CD->nz            = cc[h->rank + 1] - cc[h->rank];
+  return b_coarse + h->lv[l - 1].off * CD->kz0;
+}
+
+static pmg_status fold_allgather(pmg_mgmc h, int l, double *b_coarse, void *stream)
+{
+  const mg_level *Cc = &h->lv[l - 1];
+  const int32_t  *cc = h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1);
+  int64_t         offs[64], cnts[64];
+  PMG_CHECK(h->nranks <= 64, PMG_ERR_ARG_OUTOFRANGE, "too many ranks");
+  for (int r = 0; r < h->nranks; ++r) {
+    offs[r] = Cc->off * ((int64_t)cc[r] + 1);
+    cnts[r] = Cc->off * (int64_t)(cc[r + 1] - cc[r]);
+  }
+  return pmg_dist_allgather(h->dist, b_coarse, offs, cnts, stream);
 }
 
 /* b_coarse = P_l^T r_fine (MatRestrict).  A z-slab restricts into the coarse planes it owns (K with fine plane 2K on
@@ -1607,15 +1642,9 @@ static pmg_status mg_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coars
 {
   mg_level      *Lv = &h->lv[l], *Cc = &h->lv[l - 1];
   pmgk_st27_dims CD   = level_dims(Cc);
-  double        *bc   = b_coarse;
   const int      fold = Lv->distributed && !Cc->distributed; /* distributed -> replicated */
-  const int32_t *cc   = h->dist ? h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1) : NULL;
   if (Lv->distributed) PMG_CALL(halo_level(h, Lv, r_fine, stream));
-  if (fold) {
-    CD.kz0 = cc[h->rank];
-    CD.nz  = cc[h->rank + 1] - cc[h->rank];
-    bc     = b_coarse + Cc->off * CD.kz0; /* plane K of the full-size vector = plane K - kz0 of the shifted one */
-  }
+  double *bc = fold ? fold_own_planes(h, l, &CD, b_coarse) : b_coarse;
   if (Lv->grid_transfer) { /* matrix-free */
     pmgk_grid_layout GL;
     PMG_CALL(pmg_grid_get_kernel_layout(Lv->g, &GL));
@@ -1627,26 +1656,13 @@ static pmg_status mg_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coars
     if (Lv->dm) PMG_CALL(pmg_distmcsor_refresh_layout(Lv->dm, r_fine, stream)); /* row block: the rows of P^T read r on other ranks' rows */
     /* inside a cycle on one device the restriction also sets the zero guess of the coarse level: its rows are the rows of P^T, the
        padding of the layout is never written (zero since the allocation) -- one fill kernel less per level (PMG_MG_FUSED_ZERO=0) */
-    static int fz = -1;
-    if (fz < 0) {
-      const char *e = getenv("PMG_MG_FUSED_ZERO");
-      fz            = e ? atoi(e) : 1;
-    }
     const int needs_zero = l - 1 >= 1 || h->coarse_type != 0;
-    double   *zero = fz && needs_zero && !h->dist && !Lv->dm && !Cc->dm && b_coarse == Cc->b && Cc->mc && Lv->R_nrows == Cc->n ? Cc->x : NULL;
+    double   *zero = sw_fused_zero() && needs_zero && !h->dist && !Lv->dm && !Cc->dm && b_coarse == Cc->b && Cc->mc && Lv->R_nrows == Cc->n ? Cc->x : NULL;
     PMG_KERNEL(pmgk_csr_spmv_rows(Lv->R_nrows, Lv->R_rowpos, Lv->R_rowptr, Lv->R_col, Lv->R_val, r_fine, b_coarse, 0, zero, stream));
     if (zero) Cc->x_zeroed = 1;
     if (Lv->dm && l == h->rb_fold) PMG_CALL(rb_fold_allgather(h, b_coarse, stream)); /* the replicated level below: every rank needs the whole right-hand side */
   }
-  if (fold) {
-    int64_t offs[64], cnts[64];
-    PMG_CHECK(h->nranks <= 64, PMG_ERR_ARG_OUTOFRANGE, "too many ranks");
-    for (int r = 0; r < h->nranks; ++r) {
-      offs[r] = Cc->off * ((int64_t)cc[r] + 1);
-      cnts[r] = Cc->off * (int64_t)(cc[r + 1] - cc[r]);
-    }
-    PMG_CALL(pmg_dist_allgather(h->dist, b_coarse, offs, cnts, stream));
-  }
+  if (fold) PMG_CALL(fold_allgather(h, l, b_coarse, stream));
   return PMG_SUCCESS;
 }
 
@@ -1658,9 +1674,7 @@ static pmg_status mg_residual_restrict_slab(pmg_mgmc h, int l, void *stream)
 {
   mg_level      *Lv = &h->lv[l], *Cc = &h->lv[l - 1];
   pmgk_st27_dims CD   = level_dims(Cc);
-  double        *bc   = Cc->b;
   const int      fold = !Cc->distributed;
-  const int32_t *cc   = h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1);
   const double  *slo[2], *shi[2];
   double        *rlo[2], *rhi[2];
   int64_t        n[2];
@@ -1674,24 +1688,12 @@ static pmg_status mg_residual_restrict_slab(pmg_mgmc h, int l, void *stream)
     rhi[c] = Lv->y2hi + (int64_t)c * n[c];
   }
   PMG_CALL(pmg_dist_exchange(h->dist, 2, slo, n, rlo, n, shi, n, rhi, n, stream));
-  if (fold) {
-    CD.kz0 = cc[h->rank];
-    CD.nz  = cc[h->rank + 1] - cc[h->rank];
-    bc     = Cc->b + Cc->off * CD.kz0;
-  }
-  int done = 0;
+  double *bc   = fold ? fold_own_planes(h, l, &CD, Cc->b) : Cc->b;
+  int     done = 0;
   PMG_CALL(pmg_grid_residual_restrict(Lv->g, Lv->b, Lv->x, Lv->kz0 > 0 ? Lv->y2lo : NULL, Lv->kz0 + Lv->nzl < Lv->nz ? Lv->y2hi : NULL, &CD, bc, &done, stream));
   PMG_CHECK(done, PMG_ERR_PLIB, "level %d: the fused residual + restriction refused a slab the set-up had accepted", l);
   if (Lv->lrc) PMG_CALL(pmg_lrc_residual_sub_restricted(Lv->lrc, Cc->lrc, Lv->x, Cc->b, stream)); /* - P^T B S B^T x = - B_{l-1} (S B^T x); B^T x summed over the ranks */
-  if (fold) {
-    int64_t offs[64], cnts[64];
-    PMG_CHECK(h->nranks <= 64, PMG_ERR_ARG_OUTOFRANGE, "too many ranks");
-    for (int r = 0; r < h->nranks; ++r) {
-      offs[r] = Cc->off * ((int64_t)cc[r] + 1);
-      cnts[r] = Cc->off * (int64_t)(cc[r + 1] - cc[r]);
-    }
-    PMG_CALL(pmg_dist_allgather(h->dist, Cc->b, offs, cnts, stream));
-  }
+  if (fold) PMG_CALL(fold_allgather(h, l, Cc->b, stream));
   return PMG_SUCCESS;
 }
 
@@ -1717,7 +1719,7 @@ static pmg_status mg_prolong_add(pmg_mgmc h, int l, const double *e_coarse, doub
 }
 
 /* the low-rank update a level's sampler applies (held by the level, or by the grid object of a single-device grid level) */
-static pmg_lrc mg_level_lrc(mg_level *Lv) { return Lv->lrc ? Lv->lrc : (Lv->is_grid ? pmg_grid_lrc(Lv->g) : NULL); }
+static pmg_lrc mg_level_lrc(const mg_level *Lv) { return Lv->lrc ? Lv->lrc : (Lv->is_grid ? pmg_grid_lrc(Lv->g) : NULL); }
 
 /* The noise terms B (sqrt(S) o eta) of a cycle need one draw of k numbers per directional sweep and level
    (src/pc_mcgibbs.c:130-134) -- a launch of one wavefront in front of every sweep, ~2 us each on the cycle's critical path
@@ -1763,75 +1765,102 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
   return PMG_SUCCESS;
 }
 
+static double level_rows(const mg_level *Lv) { /* owned unknowns: a z-slab's planes, a row block's rows */ return Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n); }
+
+/* The kernels one V-cycle runs on level l, decided HERE and nowhere else: mg_vcycle launches what this says,
+   pmg_mgmc_get_algorithmic_bytes charges it.  A pure function, not a table of the set-up: the correction form and, on
+   one device, the fused transfers may be switched afterwards, and top_has_guess changes from cycle to cycle. */
+enum { MG_GUESS_KEEP, MG_GUESS_FILL, MG_GUESS_UNSET };  /* the iterate a level starts from: its own | zero, stored by a fill kernel (or by the CSR restriction into it, x_zeroed) | zero, NOT stored: the first out-of-place sweep is told */
+enum { MG_RR_TWO, MG_RR_FUSED, MG_RR_FUSED_SLAB };      /* residual, then restriction | b_{l-1} = P^T (b - A x) in one pass on one device | the same on a z-slab */
+typedef struct {
+  pmg_lrc lrc;                   /* the low-rank update the level's sampler applies, NULL if none */
+  double  rows;                  /* owned unknowns */
+  int     zero_guess;            /* MG_GUESS_* (level 0: in front of the Gibbs sweeps; the exact sampler takes no guess) */
+  int     rr;                    /* MG_RR_*, l >= 1 */
+  int     rr_lowrank_restricted; /* the residual's low-rank term is subtracted in restricted form behind the fused kernel: - P^T B S B^T x = - B_{l-1} (S B^T x) */
+  int     residual_pair;         /* class-stencil level: the paired residual kernel */
+  int     prolong_colour;        /* -1: interpolate onto both colours, else onto this one only */
+} mg_path;
+
+static mg_path level_path(const struct pmg_mgmc_s *h, int l, int top_has_guess)
+{
+  const mg_level *Lv = &h->lv[l];
+  mg_path         p  = {mg_level_lrc(Lv), level_rows(Lv), MG_GUESS_FILL, MG_RR_TWO, 0, 0, -1};
+  if (l == 0 ? h->coarse_type == 0 : (l == h->nlevels - 1 && top_has_guess)) p.zero_guess = MG_GUESS_KEEP;
+  else if (l >= 1 && st27_out_of_place(Lv) && h->nu >= 1) p.zero_guess = MG_GUESS_UNSET; /* (also under a low-rank update: the noise term changes b, the repair acts on the swept iterate) */
+  p.residual_pair = st27_use_pair(Lv) || (st27_use_pair_slab(Lv) && sw_st27_pair_slab() != 3);
+  if (l == 0) return p;
+  const mg_level *Cc = &h->lv[l - 1];
+  if (Lv->is_grid && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused) {
+    /* z-slab: agreed by the ranks at set-up, and b's ghost planes are current in the in-place form only (pmg_mgmc_sample).
+       One device: a local update on both levels and the kernel's own gate, which the launcher asks first as well */
+    const pmgk_st27_dims CD = level_dims(Cc);
+    if (Lv->distributed) p.rr = Lv->rr_slab && !h->correction_form ? MG_RR_FUSED_SLAB : MG_RR_TWO;
+    else if ((!p.lrc || (pmg_lrc_is_local(p.lrc) && Cc->is_st27 && pmg_lrc_is_local(Cc->lrc))) && pmg_grid_residual_restrict_applies(Lv->g, &CD, 0, 0)) p.rr = MG_RR_FUSED;
+  }
+  p.rr_lowrank_restricted = p.rr != MG_RR_TWO && p.lrc;
+  /* with omega = 1 a colour sweep never reads the old values of the colour it updates (the (1-omega) x term is
+     gone), so the colour the post-smoother visits first needs no correction: it is overwritten unread */
+  if (Lv->grid_transfer && h->omega == 1.0 && h->nu >= 1 && !sw_prolong_both()) p.prolong_colour = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 0 : 1;
+  return p;
+}
+
+static pmg_status mg_zero_guess(mg_level *Lv, int how, void *stream)
+{
+  if (how == MG_GUESS_UNSET) Lv->x_unset = 1;
+  else if (how == MG_GUESS_FILL && !Lv->x_zeroed) PMG_KERNEL(pmgk_fill_zero(Lv->x, Lv->ld, stream));
+  Lv->x_zeroed = 0;
+  return PMG_SUCCESS;
+}
+
 /* one multiplicative V-cycle on lv[top].b -> lv[top].x; x starts at zero on every level below the top, and on the
    top level too unless top_has_guess */
 static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_has_guess, void *stream)
 {
   const int top = h->nlevels - 1;
   uint64_t  ctr[64];
+  mg_path   path[64];
   PMG_CHECK(h->nlevels <= 64, PMG_ERR_ARG_OUTOFRANGE, "too many levels");
-  for (int l = 0; l <= top; ++l) ctr[l] = sample * MG_DRAWS_PER_SAMPLE;
-  for (int l = 0; l <= top; ++l) h->lv[l].x_zeroed = 0; /* (a cycle that ended in an error may have left one set) */
+  for (int l = 0; l <= top; ++l) {
+    ctr[l]  = sample * MG_DRAWS_PER_SAMPLE;
+    path[l] = level_path(h, l, top_has_guess);
+    h->lv[l].x_zeroed = 0; /* (a cycle that ended in an error may have left one set) */
+  }
   if (h->lrc_k > 0) PMG_CALL(mg_draw_lowrank_noise(h, seed, ctr, 1, stream));
   for (int l = top; l >= 1; --l) {
-    mg_level *Lv = &h->lv[l], *Cc = &h->lv[l - 1];
-    if (l < top || !top_has_guess) {
-      /* class-stencil levels with the out-of-place sweep: no memset, the first sweep is told that its input is zero */
-      if (Lv->x_zeroed) Lv->x_zeroed = 0;
-      else if (Lv->x2 && st27_use_pair(Lv) && h->nu >= 1) Lv->x_unset = 1; /* (also under a low-rank update: the noise term changes b, the repair acts on the swept iterate -- round 3 excluded those levels without need and paid three zero fills and twelve full phase launches per 257^3 sample) */
-      else PMG_KERNEL(pmgk_fill_zero(Lv->x, Lv->ld, stream));
-    }
-    pmg_lrc flrc = Lv->is_grid ? (Lv->lrc ? Lv->lrc : pmg_grid_lrc(Lv->g)) : NULL; /* the grid level's low-rank update (held by the level on a slab hierarchy, by the grid object otherwise) */
-    pmg_lrc slrc = Lv->is_grid ? flrc : Lv->lrc;
-    pmg_lrc_expect_residual(slrc, 1); /* the last repair of the pre-smoothing also starts the residual's low-rank term */
+    mg_level      *Lv = &h->lv[l], *Cc = &h->lv[l - 1];
+    const mg_path *p  = &path[l];
+    PMG_CALL(mg_zero_guess(Lv, p->zero_guess, stream));
+    pmg_lrc_expect_residual(p->lrc, 1); /* the last repair of the pre-smoothing also starts the residual's low-rank term */
     const pmg_status sst = mg_smooth(h, l, seed, &ctr[l], stream);
-    pmg_lrc_expect_residual(slrc, sst == PMG_SUCCESS); /* (an error: forget) */
+    pmg_lrc_expect_residual(p->lrc, sst == PMG_SUCCESS); /* (an error: forget) */
     PMG_CALL(sst);
-    if (Lv->is_grid && Lv->grid_transfer && !Lv->distributed && !Lv->cpos_dev && !h->no_fused && (!flrc || (pmg_lrc_is_local(flrc) && Cc->is_st27 && pmg_lrc_is_local(Cc->lrc)))) { /* b_{l-1} = P^T (b - A x) in one pass */
+    switch (p->rr) {
+    case MG_RR_FUSED: {
       const pmgk_st27_dims CD = level_dims(Cc);
       int                  done = 0;
       PMG_CALL(pmg_grid_residual_restrict(Lv->g, Lv->b, Lv->x, NULL, NULL, &CD, Cc->b, &done, stream));
-      if (done) {
-        if (flrc) PMG_CALL(pmg_lrc_residual_sub_restricted(flrc, Cc->lrc, Lv->x, Cc->b, stream)); /* - P^T B S B^T x = - B_{l-1} (S B^T x) */
-        continue;
-      }
+      PMG_CHECK(done, PMG_ERR_PLIB, "level %d: the fused residual + restriction refused a level its own gate had accepted", l);
+      if (p->rr_lowrank_restricted) PMG_CALL(pmg_lrc_residual_sub_restricted(p->lrc, Cc->lrc, Lv->x, Cc->b, stream));
+      break;
     }
-    if (Lv->is_grid && Lv->rr_slab && Lv->b == h->b_lay) { /* z-slab, in-place form: b's ghost planes are current */
-      PMG_CALL(mg_residual_restrict_slab(h, l, stream));
-      continue;
+    case MG_RR_FUSED_SLAB: PMG_CALL(mg_residual_restrict_slab(h, l, stream)); break;
+    default:
+      PMG_CALL(mg_residual(Lv, p->residual_pair, Lv->b, Lv->x, Lv->r, stream));
+      if (Lv->lrc) PMG_CALL(pmg_lrc_residual_sub(Lv->lrc, Lv->x, Lv->r, stream)); /* PCMGSetResidual(..., As[l]), src/pc_gamgmc.c:194; class-stencil levels and the grid level of a z-slab hierarchy: held here, not in the grid object */
+      PMG_CALL(mg_restrict(h, l, Lv->r, Cc->b, stream));
     }
-    if (Lv->is_grid) PMG_CALL(pmg_grid_residual_cvec(Lv->g, Lv->b, Lv->x, Lv->r, stream));
-    else if (Lv->is_st27) {
-      if (st27_use_pair(Lv) || (st27_use_pair_slab(Lv) && st27_pair_slab_mode() != 3)) PMG_KERNEL(pmgk_st27_residual_pair(&Lv->st, Lv->b, Lv->x, Lv->r, stream));
-      else PMG_KERNEL(pmgk_st27_residual(&Lv->st, Lv->b, Lv->x, Lv->r, stream));
-      if (Lv->lrc) PMG_CALL(pmg_lrc_residual_sub(Lv->lrc, Lv->x, Lv->r, stream)); /* PCMGSetResidual(..., As[l]), src/pc_gamgmc.c:194 */
-    }
-    else if (Lv->dm) PMG_CALL(pmg_distmcsor_residual_layout(Lv->dm, Lv->b, Lv->x, Lv->r, stream)); /* row block: + the all-reduced low-rank term */
-    else PMG_CALL(pmg_mcsor_residual_layout(Lv->mc, Lv->b, Lv->x, Lv->r, stream));
-    if (Lv->is_grid && Lv->lrc) PMG_CALL(pmg_lrc_residual_sub(Lv->lrc, Lv->x, Lv->r, stream)); /* z-slabs: the update of the fine level lives here, not in the grid object */
-    PMG_CALL(mg_restrict(h, l, Lv->r, Cc->b, stream));
   }
   {
     mg_level *C0 = &h->lv[0];
-    if (h->coarse_type == 0) {
-      PMG_CALL(pmg_chol_sample(h->chol, C0->b + C0->off, C0->x + C0->off, 1, level_seed(seed, 0), ctr[0], stream));
-    } else {
-      if (C0->x_zeroed) C0->x_zeroed = 0;
-      else PMG_KERNEL(pmgk_fill_zero(C0->x, C0->ld, stream));
-      if (C0->is_st27) PMG_CALL(st27_sample(h, C0, h->coarse_its, level_seed(seed, 0), &ctr[0], stream));
-      else PMG_CALL(pmg_mcsor_sample_layout(C0->mc, C0->b, C0->x, h->coarse_its, h->scaled, level_seed(seed, 0), ctr[0], &ctr[0], stream));
-    }
+    PMG_CALL(mg_zero_guess(C0, path[0].zero_guess, stream));
+    if (h->coarse_type == 0) PMG_CALL(pmg_chol_sample(h->chol, C0->b + C0->off, C0->x + C0->off, 1, level_seed(seed, 0), ctr[0], stream));
+    else if (C0->is_st27) PMG_CALL(mg_lowrank_sweeps(h, C0, h->coarse_its, st27_dir_sweep, level_seed(seed, 0), &ctr[0], stream));
+    else PMG_CALL(pmg_mcsor_sample_layout(C0->mc, C0->b, C0->x, h->coarse_its, h->scaled, level_seed(seed, 0), ctr[0], &ctr[0], stream));
   }
   for (int l = 1; l <= top; ++l) {
-    mg_level *Lv = &h->lv[l];
-    /* with omega = 1 a colour sweep never reads the old values of the colour it updates (the (1-omega) x term is
-       gone), so the colour the post-smoother visits first needs no correction: it is overwritten unread */
-    static int no_skip = -1;
-    if (no_skip < 0) no_skip = getenv("PMG_MG_PROLONG_BOTH") != NULL;
-    const int first = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 1 : 0;
-    const int only  = (h->omega == 1.0 && h->nu >= 1 && !no_skip) ? 1 - first : -1;
-    PMG_CALL(mg_prolong_add(h, l, h->lv[l - 1].x, Lv->x, only, stream));
-    pmg_lrc_expect_residual(mg_level_lrc(Lv), 0); /* no residual behind the post-smoothing */
+    PMG_CALL(mg_prolong_add(h, l, h->lv[l - 1].x, h->lv[l].x, path[l].prolong_colour, stream));
+    pmg_lrc_expect_residual(path[l].lrc, 0); /* no residual behind the post-smoothing */
     PMG_CALL(mg_smooth(h, l, seed, &ctr[l], stream));
   }
   if (h->lrc_k > 0) PMG_CALL(mg_draw_lowrank_noise(h, seed, ctr, 0, stream)); /* nothing outside this cycle takes its noise terms */
@@ -1865,44 +1894,33 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
   *total            = 0.0;
   for (int l = 0; l <= top; ++l) {
     const mg_level *Lv = &h->lv[l];
-    const double    N  = Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n);
-    double          by = 0.0;
-    pmg_lrc         lr = Lv->is_grid ? (Lv->lrc ? Lv->lrc : pmg_grid_lrc(Lv->g)) : Lv->lrc;
-    int32_t         k  = 0;
-    int64_t         ns = 0;
-    int             lr_dense = 0;
-    /* a rank whose slab or block misses B's support launches none of the low-rank kernels: ns = 0, no bytes (round 3 charged
-       such a rank the dense form's (24k + 48) N per sweep and inflated the summed roofline of the multi-GPU low-rank line) */
-    if (lr) pmg_lrc_get_sizes(lr, &k, &ns, &lr_dense);
+    const mg_path   p  = level_path(h, l, !h->correction_form);
+    const double    N  = p.rows;
+    int32_t         k = 0, kc = 0;
+    int64_t         ns = 0, nc = 0; /* support rows of the level's update, of the next coarser level's */
+    int             lr_dense = 0, cdense = 0;
+    /* a rank whose slab or block misses B's support launches none of the low-rank kernels: ns = 0, no bytes */
+    if (p.lrc) pmg_lrc_get_sizes(p.lrc, &k, &ns, &lr_dense);
     if (lr_dense) ns = (int64_t)N; /* dense factors: every row of the level */
     const double sweep = Lv->is_grid ? (h->omega == 1.0 ? 24.0 : 32.0) * N : (Lv->is_st27 ? 24.0 * N : 12.0 * (double)Lv->A_nnz + 40.0 * N);
-    const double lrsw  = lr ? ((8.0 * k + 24.0) + (16.0 * k + 24.0)) * (double)ns : 0.0;
+    const double lrsw  = p.lrc ? ((8.0 * k + 24.0) + (16.0 * k + 24.0)) * (double)ns : 0.0;
+    const double lrres = p.lrc ? (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns : 0.0; /* unrestricted residual term */
+    double       by    = p.zero_guess == MG_GUESS_FILL ? 8.0 * N : (p.zero_guess == MG_GUESS_UNSET ? -8.0 * N : 0.0); /* the zero fill / the first sweep does not read x */
     if (l == 0) {
-      by = h->coarse_type == 0 ? 8.0 * N * N : 8.0 * N + h->coarse_its * ndir * (sweep + lrsw);
+      by += h->coarse_type == 0 ? 8.0 * N * N : h->coarse_its * ndir * (sweep + lrsw);
     } else {
       const mg_level *Cc = &h->lv[l - 1];
-      const double    Nc = Cc->is_grid || Cc->padded ? (double)Cc->nx * Cc->ny * Cc->nzl : (double)(Cc->rb ? Cc->rb_nowned : Cc->n);
-      const int has_guess = l == top && !h->correction_form;
-      const int unset     = !has_guess && Lv->x2 && st27_use_pair(Lv) && h->nu >= 1; /* zero-guess out-of-place sweep */
+      const double    Nc = level_rows(Cc);
       by += 2.0 * nsw * (sweep + lrsw);
-      if (!has_guess) by += unset ? -8.0 * N : 8.0 * N; /* the first sweep does not read x / the zero fill */
-      const int fused = Lv->is_grid && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused &&
-                        (Lv->distributed ? Lv->rr_slab && !h->correction_form : (!lr || (pmg_lrc_is_local(lr) && Cc->is_st27 && pmg_lrc_is_local(Cc->lrc))));
-      if (fused) by += 16.0 * N + 8.0 * Nc;
+      if (p.rr != MG_RR_TWO) by += 16.0 * N + 8.0 * Nc;
       else if (Lv->is_grid || Lv->is_st27) by += 24.0 * N + 8.0 * N + 8.0 * Nc;
       else by += 12.0 * (double)Lv->A_nnz + 28.0 * N + 12.0 * (double)Lv->P_nnz + 12.0 * Nc + 8.0 * N;
-      if (lr) {
-        int32_t kc = 0;
-        int64_t nc = 0;
-        int     cdense = 0;
-        if (Cc->lrc) pmg_lrc_get_sizes(Cc->lrc, &kc, &nc, &cdense);
-        if (fused && Cc->lrc && !cdense) by += (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)nc;
-        else by += (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns;
-      }
-      const int one_colour = Lv->is_grid && h->omega == 1.0 && h->nu >= 1 && !getenv("PMG_MG_PROLONG_BOTH");
-      if (Lv->grid_transfer || Lv->nat_transfer) by += (one_colour ? 8.0 : 16.0) * N + 8.0 * Nc;
+      if (p.rr_lowrank_restricted && Cc->lrc) pmg_lrc_get_sizes(Cc->lrc, &kc, &nc, &cdense);
+      if (p.rr_lowrank_restricted && Cc->lrc && !cdense) by += (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)nc;
+      else by += lrres;
+      if (Lv->grid_transfer || Lv->nat_transfer) by += (p.prolong_colour >= 0 ? 8.0 : 16.0) * N + 8.0 * Nc;
       else by += 12.0 * (double)Lv->P_nnz + 20.0 * N + 8.0 * Nc;
-      if (l == top && h->correction_form) by += 48.0 * N + (lr ? (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns : 0.0);
+      if (l == top && h->correction_form) by += 48.0 * N + lrres;
     }
     if (per_level) per_level[l] = by;
     *total += by;
@@ -1929,7 +1947,7 @@ pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32
   PMG_CALL(lvl_to_layout(F, b_nat, h->b_lay, stream));
   PMG_CALL(lvl_to_layout(F, y_nat, h->y_lay, stream));
   if (h->correction_form && F->distributed) PMG_CALL(halo_level(h, F, h->y_lay, stream)); /* the outer residual reads the ghost planes of y */
-  if (!h->correction_form && F->rr_slab) PMG_CALL(halo_level(h, F, h->b_lay, stream));     /* the fused residual + restriction reads b on the ghost planes */
+  if (level_path(h, h->nlevels - 1, 1).rr == MG_RR_FUSED_SLAB) PMG_CALL(halo_level(h, F, h->b_lay, stream)); /* the fused residual + restriction reads b on the ghost planes */
   if (h->correction_form && F->dm) PMG_CALL(pmg_distmcsor_refresh_layout(F->dm, h->y_lay, stream)); /* ... the ghost rows of a row block */
   for (int32_t it = 0; it < its; ++it) {
     if (!h->correction_form) {
@@ -1949,10 +1967,8 @@ pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32
       PMG_CALL(mg_vcycle(h, seed, counter0 + (uint64_t)it, 0, stream));
       PMG_HIP(hipMemcpyAsync(h->y_lay, F->x, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     } else { /* w = b - A y; work = MG(w); y += work, src/pc_gamgmc.c:253-256 */
-      if (F->is_grid) PMG_CALL(pmg_grid_residual_cvec(F->g, h->b_lay, h->y_lay, F->b, stream));
-      else if (F->dm) PMG_CALL(pmg_distmcsor_residual_layout(F->dm, h->b_lay, h->y_lay, F->b, stream));
-      else PMG_CALL(pmg_mcsor_residual_layout(F->mc, h->b_lay, h->y_lay, F->b, stream));
-      if (F->is_grid && F->lrc) PMG_CALL(pmg_lrc_residual_sub(F->lrc, h->y_lay, F->b, stream)); /* z-slabs */
+      PMG_CALL(mg_residual(F, 0, h->b_lay, h->y_lay, F->b, stream));
+      if (F->lrc) PMG_CALL(pmg_lrc_residual_sub(F->lrc, h->y_lay, F->b, stream)); /* z-slabs */
       PMG_CALL(mg_vcycle(h, seed, counter0 + (uint64_t)it, 0, stream));
       PMG_KERNEL(pmgk_axpy(F->ld, 1.0, F->x, h->y_lay, stream));
     }
@@ -2234,7 +2250,7 @@ pmg_status pmg_mgmc_level_sweep(pmg_mgmc h, int32_t level, int backward, int noi
   PMG_CHECK(Lv->is_st27, PMG_ERR_SUP, "level %d: only class-stencil levels (use pmg_grid_* / pmg_mcsor_* for the others)", level);
   pmgk_st27 S = Lv->st;
   S.sqrtdiag  = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;
-  if (Lv->x2 && st27_use_pair(Lv)) { /* the production kernel: out of place into the level's second buffer, then copied back */
+  if (st27_out_of_place(Lv)) { /* the production kernel: out of place into the level's second buffer, then copied back */
     PMG_KERNEL(pmgk_st27_sweep_pp(&S, backward != 0, h->omega, noisy != 0, seed, counter, b_lvl, x_lvl, Lv->x2, stream));
     PMG_HIP(hipMemcpyAsync(x_lvl, Lv->x2, sizeof(double) * (size_t)Lv->ld, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return PMG_SUCCESS;
@@ -2248,14 +2264,9 @@ pmg_status pmg_mgmc_level_residual(pmg_mgmc h, int32_t level, const double *b_lv
   mg_level *Lv;
   PMG_CALL(level_checked(h, level, 0, &Lv));
   PMG_CHECK(b_lvl && x_lvl && r_lvl, PMG_ERR_ARG_NULL, "null vector");
-  if (Lv->is_grid) return pmg_grid_residual_cvec(Lv->g, b_lvl, x_lvl, r_lvl, stream);
-  if (Lv->is_st27) {
-    if (st27_use_pair(Lv)) PMG_KERNEL(pmgk_st27_residual_pair(&Lv->st, b_lvl, x_lvl, r_lvl, stream));
-    else PMG_KERNEL(pmgk_st27_residual(&Lv->st, b_lvl, x_lvl, r_lvl, stream));
-    return PMG_SUCCESS;
-  }
+  if (Lv->is_grid || Lv->is_st27) return mg_residual(Lv, level_path(h, level, 0).residual_pair, b_lvl, x_lvl, r_lvl, stream);
   PMG_CHECK(Lv->mc, PMG_ERR_SUP, "level %d has no residual kernel", level);
-  return pmg_mcsor_residual_layout(Lv->mc, b_lvl, x_lvl, r_lvl, stream);
+  return pmg_mcsor_residual_layout(Lv->mc, b_lvl, x_lvl, r_lvl, stream); /* (of a row block: the local rows, no exchange) */
 }
 
 /* b_coarse (level-1) = P^T r_fine (level); x_fine (level) += P e_coarse (level-1), both colours */
@@ -2295,7 +2306,7 @@ pmg_status pmg_mgmc_level_prolong_add(pmg_mgmc h, int32_t level, const double *e
 static pmg_status level_lrc(pmg_mgmc h, int32_t level, int need_coarser, mg_level **Lv, pmg_lrc *l)
 {
   PMG_CALL(level_checked(h, level, need_coarser, Lv));
-  *l = (*Lv)->is_grid ? ((*Lv)->lrc ? (*Lv)->lrc : pmg_grid_lrc((*Lv)->g)) : (*Lv)->lrc;
+  *l = mg_level_lrc(*Lv);
   PMG_CHECK(*l, PMG_ERR_ARG_WRONGSTATE, "level %d carries no low-rank update", level);
   return PMG_SUCCESS;
 }
