@@ -665,6 +665,46 @@ pmg_status pmg_gelman_rubin(int32_t chains, int64_t n, const double *vals_host, 
 /* the same on steps [first, first + count) of the trace of QOI q */
 pmg_status pmg_chainstats_rhat(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, double *gr);
 
+/* ---- covariance error over the chains on the device: the study of examples/ex6.c --------------------------------- */
+/* The ex6 consumer of pmg_*_sample_chains: EstimateCovarianceMatErrors (src/stats.c:94-117; examples/ex6.c:193) for chains
+   that live on the device.  Fed one step's Y (n x nchains, chain fastest, natural rows: what pmg_chains_callback hands out),
+   it records err[step] = ||C_step - Sigma||_F / ||Sigma||_F with C_step the unbiased 1 / (nchains - 1) covariance over the
+   chains (SampleMean, src/stats.c:55-61; SampleCovariance, :63-84) and Sigma a dense symmetric reference held on the device
+   (DenseInverse, :8-31).  No sample and no n x n matrix leaves the device; in the trace path the covariance is never written
+   to memory: row means, then a symmetric rank-nchains update of centred rows on the f64 matrix cores that leaves one double per
+   32 x 32 tile of the lower triangle, then one reduction (:110-112).  The order of every sum is a function of (n, nchains)
+   alone (stated in kernels_chaincov.hip and DESIGN 11.3): no floating-point atomics, the same bits on every run and stream.
+   Single device.  PMG_ERR_SUP: n > 4096 (as pmg_estimate_covariance_errors); PMG_ERR_ARG_OUTOFRANGE: n < 1, nchains < 2
+   (src/stats.c:78 divides by chains - 1), max_steps < 1 (max_steps sizes the trace).  All argument checks run before any
+   device work.  Calls on one handle must be ordered (one stream, or synchronised): they share its scratch. */
+typedef struct pmg_chaincov_s *pmg_chaincov;
+/* Sigma = L^-T L^-1 formed on the device from the L^-1 the handle stores (DenseInverse of the factored matrix, src/stats.c:8-31):
+   A^-1 for pmg_chol_create_csr, (A + B S B^T)^-1 for pmg_chol_create_csr_lowrank.  The handle keeps its own Sigma: ch may be
+   destroyed afterwards. */
+pmg_status pmg_chaincov_create_chol(pmg_chol ch, int32_t nchains, int32_t max_steps, pmg_chaincov *cc);
+/* any symmetric reference, n x n host doubles (copied; uploaded by the first update: creation touches no device) */
+pmg_status pmg_chaincov_create_dense(int32_t n, const double *Sigma_host, int32_t nchains, int32_t max_steps, pmg_chaincov *cc);
+pmg_status pmg_chaincov_destroy(pmg_chaincov *cc);
+/* the stream the callback below launches on (it carries none): the one the sampler is called with */
+pmg_status pmg_chaincov_set_stream(pmg_chaincov cc, void *stream);
+/* one step of all chains (one sample index of src/stats.c:108-113).  PMG_ERR_ARG_OUTOFRANGE once max_steps updates have been
+   made since creation or the last reset. */
+pmg_status pmg_chaincov_update(pmg_chaincov cc, const double *Y_dev, void *stream);
+/* ready-made pmg_chains_callback, ctx = the handle (the SampleCallback of examples/ex6.c:183 without the copies).
+   PMG_ERR_ARG_SIZ when the sampler's sizes are not the handle's. */
+int pmg_chaincov_callback(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
+/* forget the trace (Sigma stays); waits for updates in flight */
+pmg_status pmg_chaincov_reset(pmg_chaincov cc);
+pmg_status pmg_chaincov_get_count(pmg_chaincov cc, int32_t *steps);
+/* errs of steps [first, first + count) as host doubles (the errs array of examples/ex6.c:191-193).  Synchronises the device.
+   PMG_ERR_ARG_OUTOFRANGE: the window outside what has been recorded. */
+pmg_status pmg_chaincov_get_errors(pmg_chaincov cc, int32_t first, int32_t count, double *errs_host);
+/* the reference Sigma, n x n host doubles (symmetric) */
+pmg_status pmg_chaincov_get_reference(pmg_chaincov cc, double *Sigma_host);
+/* one step's full covariance (SampleCovariance, src/stats.c:63-84) into C_dev, n x n device doubles, both triangles, exactly
+   symmetric; records nothing */
+pmg_status pmg_chaincov_covariance(pmg_chaincov cc, const double *Y_dev, double *C_dev, void *stream);
+
 /* ------------------------------------------------------------------------------------------------------ */
 /* The registration boundary without PETSc: PCRegister / PCSetType / pc->ops / PCSetSampleCallback /        */
 /* PCSHELL / KSPRICHARDSON on raw device arrays (reference src/parmgmc.c:44-54,118-151; examples/ex1.c,     */

@@ -286,6 +286,17 @@ _sig = {
     "pmg_chainstats_get_trace": (_int, [_vp, _i32, _i32, _i32, _vp]),
     "pmg_gelman_rubin": (_int, [_i32, _i64, _vp, C.POINTER(_dbl)]),
     "pmg_chainstats_rhat": (_int, [_vp, _i32, _i32, _i32, C.POINTER(_dbl)]),
+    "pmg_chaincov_create_chol": (_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
+    "pmg_chaincov_create_dense": (_int, [_i32, _vp, _i32, _i32, C.POINTER(_vp)]),
+    "pmg_chaincov_destroy": (_int, [C.POINTER(_vp)]),
+    "pmg_chaincov_set_stream": (_int, [_vp, _vp]),
+    "pmg_chaincov_update": (_int, [_vp, _vp, _vp]),
+    "pmg_chaincov_callback": (_int, [_i32, _vp, _i32, _i32, _vp]),
+    "pmg_chaincov_reset": (_int, [_vp]),
+    "pmg_chaincov_get_count": (_int, [_vp, C.POINTER(_i32)]),
+    "pmg_chaincov_get_errors": (_int, [_vp, _i32, _i32, _vp]),
+    "pmg_chaincov_get_reference": (_int, [_vp, _vp]),
+    "pmg_chaincov_covariance": (_int, [_vp, _vp, _vp, _vp]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

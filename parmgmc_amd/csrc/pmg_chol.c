@@ -133,6 +133,9 @@ pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *
   return PMG_SUCCESS;
 }
 
+int32_t       pmg_chol_size(pmg_chol ch) { return ch->n; }
+const double *pmg_chol_inverse_factor_upper(pmg_chol ch) { return ch->W_up; }
+
 pmg_status pmg_chol_destroy(pmg_chol *ch)
 {
   if (!ch || !*ch) return PMG_SUCCESS;

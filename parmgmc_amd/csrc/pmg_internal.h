@@ -107,6 +107,9 @@ pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc); /* PMG_ERR_SUP for what the
 const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc);      /* layout -> natural row map on the device (-1 in pad rows) */
 /* pmg_chol.c: the exact sample y = L^-T (L^-1 b + xi) on C right-hand sides; Xi, V: n x C work arrays */
 pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *B, double *Y, double *Xi, double *V, void *stream);
+/* the handle's size and its (L^-1)^T: device, n x n row-major, zero below the diagonal (borrowed) */
+int32_t       pmg_chol_size(pmg_chol ch);
+const double *pmg_chol_inverse_factor_upper(pmg_chol ch);
 
 /* pmg_rowblock.c */
 void pmg_mcsor_adopt_arrays(pmg_mcsor mc, int32_t *rowptr, int32_t *colidx, double *vals);

@@ -216,6 +216,15 @@ void pmgk_chainstats_geometry(int64_t n, int32_t nchains, int32_t *iters, int32_
 int  pmgk_chainstats_update(int64_t n, int32_t nchains, int nqoi, const pmgk_chainstats_qoi *Q, double count, const double *Y, double *mean, double *M2, double *partial, double *trace_step, int64_t qstride, void *stream);
 int  pmgk_chainstats_fields(int64_t n, double count, const double *mean, const double *M2, double *mean_out, double *var_out, void *stream);
 
+/* covariance over the chains (kernels_chaincov.hip): Y is n x K, k fastest; Sigma and Cout n x n row-major; partial holds
+   pmgk_chaincov_ntiles(n) doubles, one per 32 x 32 tile of the lower triangle; every sum in an order that (n, K) alone fixes */
+int pmgk_chaincov_ntiles(int32_t n);
+int pmgk_chaincov_means(int32_t n, int32_t K, const double *Y, double *mean, void *stream);
+int pmgk_chaincov_syrk_error(int32_t n, int32_t K, const double *Y, const double *mean, double denom, const double *Sigma, double *partial, void *stream);
+int pmgk_chaincov_syrk_matrix(int32_t n, int32_t K, const double *Y, const double *mean, double denom, double *Cout, void *stream);
+int pmgk_chaincov_sqnorm_tiles(int32_t n, const double *Sigma, double *partial, void *stream);
+int pmgk_chaincov_reduce(int ntiles, const double *partial, const double *norm, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

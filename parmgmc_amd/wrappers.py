@@ -460,19 +460,25 @@ class MGMC:
         check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, None, _stream()))
         return out.value
 
-    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None, stats=None) -> int:
+    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None, stats=None, cov=None) -> int:
         """`its` samples of C chains on a hierarchy from from_hierarchy: Y is a contiguous (n, C) float64 tensor, b one vector
         (n,) shared by all chains or one per chain (n, C); column c equals sample(b or b[:, c], Y[:, c], its, seeds[c], ...) bit
         for bit.  callback(it, Y) after every sample; a raised exception aborts the loop.  stats: a ChainStats(n, C) updated
-        after every sample by the library's own callback instead (no Python in the loop; excludes callback)."""
+        after every sample by the library's own callback instead (no Python in the loop; excludes callback).  cov: a
+        ChainCov(n, C) that records the covariance error of every sample the same way; stats= and cov= together are updated by
+        one Python-level callback."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
         cb, ctx = None, None
-        if stats is not None:
-            if callback is not None:
-                raise ValueError("stats= and callback= exclude each other")
+        if (stats is not None or cov is not None) and callback is not None:
+            raise ValueError("stats= / cov= and callback= exclude each other")
+        if stats is not None and cov is not None:
+            callback = _update_both(stats, cov, self.n, nc)
+        elif stats is not None:
             cb, ctx = stats._as_callback(self.n, nc, lib.pmg_chainstats_callback)
+        elif cov is not None:
+            cb, ctx = cov._as_callback(self.n, nc)
         if callback is not None:
 
             def _cb(it, ptr, n, nchains, _ctx):
@@ -553,16 +559,19 @@ class WoodburySampler:
                 callback(it, y)
         return counter0 + its
 
-    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None, stats=None) -> int:
+    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None, stats=None, cov=None) -> int:
         """run() on C chains of one device: Y is a contiguous (n, C) float64 tensor, b one vector (n,) shared by the chains;
         column c equals run(b, Y[:, c], its, seeds[c], counter0) bit for bit when sample_chains(W, Y, counter) advances every
         column c of Y as sample(W[:, c], Y[:, c], counter) does -- e.g. MGMC.sample_chains with per-chain right-hand sides.
-        callback(it, Y) after every sample, or stats.update(Y) for a ChainStats(n, C) (not both)."""
+        callback(it, Y) after every sample, or stats.update(Y) for a ChainStats(n, C) and / or cov.update(Y) for a
+        ChainCov(n, C) (not both kinds)."""
         import torch
 
-        if stats is not None and callback is not None:
-            raise ValueError("stats= and callback= exclude each other")
+        if (stats is not None or cov is not None) and callback is not None:
+            raise ValueError("stats= / cov= and callback= exclude each other")
         p, nc = _chains(Y, self.n)
+        if cov is not None:
+            cov._check_sizes(self.n, nc)
         sample_chains = sample_chains or self._sample_chains
         assert sample_chains is not None, "run_chains needs sample_chains(W, Y, counter)"
         keys = _seeds([int(v) ^ 0x5851F42D4C957F2D for v in _seeds(seeds, nc)], nc)
@@ -574,6 +583,8 @@ class WoodburySampler:
             check(lib.pmg_woodbury_correct_chains(self._h, nc, p, _stream()))
             if stats is not None:
                 stats.update(Y)
+            if cov is not None:
+                cov.update(Y)
             if callback is not None:
                 callback(it, Y)
         return counter0 + its
@@ -670,6 +681,109 @@ class ChainStats:
             self.destroy()
         except Exception:
             pass
+
+
+class ChainCov:
+    """pmg_chaincov: the covariance error of every step's chains against a dense reference, kept on the device --
+    err[step] = ||C_step - Sigma||_F / ||Sigma||_F with C_step the unbiased covariance over the chains (replaces
+    EstimateCovarianceMatErrors, reference src/stats.c:94-117, on the host copies of examples/ex6.c:168-193).  Build with
+    from_chol / from_csr (Sigma = the inverse of the factored matrix, formed on the device) or from_dense (any symmetric Sigma)."""
+
+    def __init__(self, handle, n: int, nchains: int, max_steps: int):
+        self._h, self.n, self.nchains, self.max_steps = handle, int(n), int(nchains), int(max_steps)
+
+    @classmethod
+    def from_chol(cls, chol, nchains: int, max_steps: int = 1000):
+        """Sigma = L^-T L^-1 of a CholSampler (prior, or posterior when it was built with B, S); chol may be destroyed afterwards"""
+        h = C.c_void_p()
+        check(lib.pmg_chaincov_create_chol(chol._h, nchains, max_steps, C.byref(h)))
+        return cls(h, chol.n, nchains, max_steps)
+
+    @classmethod
+    def from_csr(cls, rowptr, colidx, vals, nchains: int, max_steps: int = 1000, lowrank=None):
+        """Sigma = A^-1, or (A + B diag(S) B^T)^-1 with lowrank = (B, S)"""
+        B, S = lowrank if lowrank is not None else (None, None)
+        chol = CholSampler(rowptr, colidx, vals, B, S)
+        try:
+            return cls.from_chol(chol, nchains, max_steps)
+        finally:
+            chol.destroy()
+
+    @classmethod
+    def from_dense(cls, Sigma, nchains: int, max_steps: int = 1000):
+        """any symmetric (n, n) reference on the host; uploaded by the first update"""
+        Sg = np.ascontiguousarray(Sigma, np.float64)
+        assert Sg.ndim == 2 and Sg.shape[0] == Sg.shape[1], "need a square matrix"
+        h = C.c_void_p()
+        check(lib.pmg_chaincov_create_dense(Sg.shape[0], Sg.ctypes.data, nchains, max_steps, C.byref(h)))
+        return cls(h, Sg.shape[0], nchains, max_steps)
+
+    def _check_sizes(self, n: int, nchains: int):
+        assert (n, nchains) == (self.n, self.nchains), f"ChainCov of {self.n} x {self.nchains} on samples of {n} x {nchains}"
+
+    def update(self, Y):
+        """one step: Y is a contiguous (n, C) float64 CUDA tensor, on the current stream"""
+        assert tuple(Y.shape) == (self.n, self.nchains), f"need an ({self.n}, {self.nchains}) tensor"
+        check(lib.pmg_chaincov_update(self._h, _ptr(Y), _stream()))
+
+    def _as_callback(self, n: int, nchains: int):
+        """(function pointer, context) for a sampler's chains callback; the callback launches on the current stream"""
+        self._check_sizes(n, nchains)
+        check(lib.pmg_chaincov_set_stream(self._h, _stream()))
+        return C.cast(lib.pmg_chaincov_callback, C.c_void_p), self._h
+
+    def reset(self):
+        check(lib.pmg_chaincov_reset(self._h))
+
+    def count(self) -> int:
+        st = C.c_int32()
+        check(lib.pmg_chaincov_get_count(self._h, C.byref(st)))
+        return st.value
+
+    def errors(self, first: int = 0, count=None) -> np.ndarray:
+        """the errors of the steps [first, first + count) as a host array; count = None: all recorded steps from first"""
+        if count is None:
+            count = max(self.count() - first, 0)
+        out = np.empty(max(count, 0))
+        check(lib.pmg_chaincov_get_errors(self._h, first, count, out.ctypes.data))
+        return out
+
+    def reference(self) -> np.ndarray:
+        """Sigma as a host (n, n) array"""
+        out = np.empty((self.n, self.n))
+        check(lib.pmg_chaincov_get_reference(self._h, out.ctypes.data))
+        return out
+
+    def covariance(self, Y):
+        """the unbiased covariance over the chains of one step as an (n, n) device tensor (both triangles); records nothing"""
+        import torch
+
+        assert tuple(Y.shape) == (self.n, self.nchains), f"need an ({self.n}, {self.nchains}) tensor"
+        out = torch.empty((self.n, self.n), dtype=torch.float64, device="cuda")
+        check(lib.pmg_chaincov_covariance(self._h, _ptr(Y), _ptr(out), _stream()))
+        return out
+
+    def destroy(self):
+        if self._h:
+            check(lib.pmg_chaincov_destroy(C.byref(self._h)))
+
+    def __del__(self):
+        try:
+            self.destroy()
+        except Exception:
+            pass
+
+
+def _update_both(stats, cov, n: int, nchains: int):
+    """a Python-level chains callback that feeds a ChainStats and a ChainCov of the sampler's sizes"""
+    assert (n, nchains) == (stats.n, stats.nchains), f"ChainStats of {stats.n} x {stats.nchains} on samples of {n} x {nchains}"
+    cov._check_sizes(n, nchains)
+
+    def both(it, Y):
+        stats.update(Y)
+        cov.update(Y)
+
+    return both
 
 
 def gelman_rubin(vals) -> float:

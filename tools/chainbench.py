@@ -16,6 +16,12 @@ within --radius of centre j, divided by their count): the MATLRC sweep (mcgibbs,
 operator with pmg_mcsor_set_lowrank) and Woodbury + MGMC chains (WoodburySampler.run_chains on the per-chain right-hand-side
 MGMC call), each beside its single-chain entry point (mcsor sample; the WoodburySampler.run loop).
 
+--cov: the covariance-error lines instead (pmg_chaincov_update; the config-4 mesh is not built): for n in {1024, 4096} x C in
+{32, 1000}, time per update (median of `regions` event-timed groups of 20 updates), n (n + 1) C flops over that time against the
+78.6 TFLOP/s f64 matrix peak of the vendor's data sheet, and at n = 1024 the host path on the same data: the device -> host copy of Y
+plus pmg_estimate_covariance_errors per sample index (two indices minus one, so that its dense inverse is not counted); then MGMC
+chains on the ex6 operator (32 x 32, kappa 1e-2, the hierarchy of the ex6 tests) at C = 1000 with and without cov=.
+
 Time per call = median over `regions` event-timed regions of one call of `its` samples each.  Aggregate rate = C * its /
 time.  Roofline fraction = algorithmic bytes (sweep: 12 nnz + 24 N + 16 N C; MGMC: pmg_mgmc_get_algorithmic_bytes_chains)
 / time, against 8 TB/s.  One JSON line per chain count."""
@@ -57,7 +63,11 @@ def main():
     ap.add_argument("--lowrank", type=int, default=0, help="K > 0: the posterior lines with K ball observations")
     ap.add_argument("--radius", type=float, default=0.1)
     ap.add_argument("--stats", action="store_true", help="the chain-statistics lines (pmg_chainstats_update)")
+    ap.add_argument("--cov", action="store_true", help="the covariance-error lines (pmg_chaincov_update)")
+    ap.add_argument("--cov-updates-only", action="store_true", help="with --cov: only the update groups (for runs under rocprofv3)")
     args = ap.parse_args()
+    if args.cov:
+        return cov_lines(args)
 
     import torch
 
@@ -205,6 +215,67 @@ def stats_lines(args, n, mg, b):
                           "added_us_per_sample": (with_stats[0] - plain[0]) / its * 1e3, "steps_recorded": cs.count()[0]}), flush=True)
         del Y, cs
         torch.cuda.empty_cache()
+
+
+F64_MATRIX_PEAK = 78.6e12  # MI355X data sheet, FP64 matrix
+
+
+def cov_lines(args):
+    import numpy as np
+    import torch
+
+    import oracle as O
+    from parmgmc_amd import MGMC, ChainCov, estimate_covariance_errors
+    from parmgmc_amd.unstructured import build_hierarchy
+
+    reps = 20
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    for n in (1024, 4096):
+        for C in (32, 1000):
+            Y = torch.randn((n, C), dtype=torch.float64, device="cuda", generator=gen)
+            cc = ChainCov.from_dense(np.eye(n), C, max_steps=reps * (args.regions + 1))
+
+            def group():
+                for _ in range(reps):
+                    cc.update(Y)
+
+            med, lo, hi = (t / reps for t in timed_all(group, args.regions))
+            flops = float(n) * (n + 1) * C
+            rec = {"n": n, "chains": C, "update_us": med * 1e3, "update_spread_us": [lo * 1e3, hi * 1e3], "flops": flops, "TFLOPs": flops / med / 1e9,
+                   "fraction_of_f64_matrix_peak": flops / (med * 1e-3) / F64_MATRIX_PEAK, "steps_recorded": cc.count()}
+            if n == 1024 and not args.cov_updates_only:
+                A = O.ex6_matrix(32, 1e-2)
+                t0 = time.perf_counter()
+                Yh = Y.T.contiguous().cpu().numpy()
+                copy_ms = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                estimate_covariance_errors(A.rowptr, A.colidx, A.vals, Yh, C)
+                one = time.perf_counter() - t0
+                t0 = time.perf_counter()
+                estimate_covariance_errors(A.rowptr, A.colidx, A.vals, np.concatenate([Yh, Yh]), C)
+                two = time.perf_counter() - t0
+                host_ms = (two - one) * 1e3
+                rec.update({"host_copy_ms": copy_ms, "host_ms_per_index": host_ms, "host_first_index_ms_with_inverse": one * 1e3, "host_over_device": (copy_ms + host_ms) / med})
+            print(json.dumps(rec), flush=True)
+            del Y, cc
+            torch.cuda.empty_cache()
+    if args.cov_updates_only:
+        return
+    A = O.ex6_matrix(32, 1e-2)
+    ops, ps = build_hierarchy(A.scipy().tocsr(), coarse_max=100)
+    mg = MGMC.from_hierarchy(ops, ps)
+    mg.set_smoother(True, 1.0, 1, 1)
+    mg.setup()
+    n, C, its = A.n, 1000, args.its
+    seeds = [0x5EED0000 + 7919 * c for c in range(C)]
+    b = torch.zeros(n, dtype=torch.float64, device="cuda")
+    Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+    cc = ChainCov.from_csr(A.rowptr, A.colidx, A.vals, C, max_steps=its * (args.regions + 1))
+    plain = timed_all(lambda: mg.sample_chains(b, Y, its, seeds), args.regions)
+    with_cov = timed_all(lambda: mg.sample_chains(b, Y, its, seeds, cov=cc), args.regions)
+    print(json.dumps({"operator": "ex6 32 x 32", "chains": C, "its": its, "mgmc_ms_per_sample": plain[0] / its, "mgmc_spread_ms_per_sample": [plain[1] / its, plain[2] / its],
+                      "mgmc_cov_ms_per_sample": with_cov[0] / its, "mgmc_cov_spread_ms_per_sample": [with_cov[1] / its, with_cov[2] / its],
+                      "added_us_per_sample": (with_cov[0] - plain[0]) / its * 1e3, "steps_recorded": cc.count(), "last_error": float(cc.errors()[-1])}), flush=True)
 
 
 def ball_centres(xy, k):
