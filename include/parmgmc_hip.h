@@ -20,6 +20,10 @@
  *     local sizes do not fit fails with PETSC_ERR_ARG_OUTOFRANGE.  Scalars are double (PetscScalar = PetscReal).
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream).  All device work is enqueued on
  *     it and NOT synchronised: calls return as soon as the work is queued unless stated otherwise.
+ *     One exception holds for every object: a call that has to allocate or grow the object's device workspace (the
+ *     first call of its kind on the object, a larger nchains, the first per-chain right-hand side) or to replace the
+ *     seeds of a chains call synchronises `stream`, and returns only when the new buffers are zero-filled; with the
+ *     sizes and seeds of an earlier call nothing synchronises.
  *   - objects are not thread safe (the reference is single threaded per rank, src/parmgmc.c:38-42).
  */
 #ifndef PARMGMC_HIP_H

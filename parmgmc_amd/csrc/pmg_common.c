@@ -23,13 +23,22 @@ const char *pmg_last_error_string(void) { return pmg_errbuf; }
 const char *pmg_version(void) { return PMG_VERSION_STRING; }
 const char *pmg_gpu_arch(void) { return "gfx950"; }
 
+/* Zero fill that has finished when the call returns.  hipMemset runs on the null stream and may return before the fill is
+   done; a caller's non-blocking stream is not ordered against the null stream, so a kernel enqueued there right afterwards
+   could write the buffer first and have its values zeroed.  Waiting for the null stream closes that window. */
+pmg_status pmg_dev_zero(void *p, size_t bytes)
+{
+  PMG_HIP(hipMemset(p, 0, bytes));
+  PMG_HIP(hipStreamSynchronize(NULL));
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_dev_alloc(void **p, size_t bytes)
 {
   *p = NULL;
   if (bytes == 0) bytes = 8;
   PMG_HIP(hipMalloc(p, bytes));
-  PMG_HIP(hipMemset(*p, 0, bytes));
-  return PMG_SUCCESS;
+  return pmg_dev_zero(*p, bytes);
 }
 
 pmg_status pmg_dev_upload(void **p, const void *host, size_t bytes)

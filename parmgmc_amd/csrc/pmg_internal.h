@@ -86,7 +86,8 @@ pmg_status pmg_narrow_csr(int64_t nrows, int64_t ncols, const void *rowptr, cons
 void pmg_trace_begin(const char *name);
 void pmg_trace_end(void);
 /* device allocation helpers (zero-filled) */
-pmg_status pmg_dev_alloc(void **p, size_t bytes);
+pmg_status pmg_dev_alloc(void **p, size_t bytes); /* zero-filled; the fill has finished on return */
+pmg_status pmg_dev_zero(void *p, size_t bytes);   /* zero fill, finished on return */
 pmg_status pmg_dev_upload(void **p, const void *host, size_t bytes);
 void       pmg_dev_free(void *p);
 

@@ -933,7 +933,7 @@ static pmg_status mgmc_setup_user(pmg_mgmc h)
       mg_level *Cc = &h->lv[l - 1];
       double   *Bc = NULL;
       PMG_CALL(pmg_dev_alloc((void **)&Bc, sizeof(double) * (size_t)Cc->ld * (size_t)h->lrc_k));
-      PMG_HIP(hipMemset(Bc, 0, sizeof(double) * (size_t)Cc->ld * (size_t)h->lrc_k));
+      PMG_CALL(pmg_dev_zero(Bc, sizeof(double) * (size_t)Cc->ld * (size_t)h->lrc_k));
       for (int32_t c = 0; c < h->lrc_k; ++c) {
         double *bf = Bdev + (size_t)U->ld * c, *bc = Bc + (size_t)Cc->ld * c;
         PMG_CALL(pmg_distmcsor_refresh_layout(U->dm, bf, NULL)); /* the rows of P^T read other ranks' rows of B */
@@ -1362,7 +1362,7 @@ static pmg_status stencil_attach_lowrank(pmg_mgmc h, double **B0_host)
   const int32_t nrows = h->dist ? h->n_io : F->n;
   *B0_host            = NULL;
   PMG_CALL(pmg_dev_alloc((void **)&Bcur, sizeof(double) * (size_t)F->ld * k));
-  PMG_HIP(hipMemset(Bcur, 0, sizeof(double) * (size_t)F->ld * k));
+  PMG_CALL(pmg_dev_zero(Bcur, sizeof(double) * (size_t)F->ld * k));
   PMG_CALL(pmg_dev_alloc((void **)&tmp, sizeof(double) * (size_t)nrows));
   for (int c = 0; c < k; ++c) { /* natural host column (this rank's planes) -> cvec */
     PMG_HIP(hipMemcpy(tmp, h->lrc_B + (size_t)nrows * c, sizeof(double) * (size_t)nrows, hipMemcpyHostToDevice));
@@ -1376,7 +1376,7 @@ static pmg_status stencil_attach_lowrank(pmg_mgmc h, double **B0_host)
     mg_level *Lv = &h->lv[l], *Cc = &h->lv[l - 1];
     double   *Bnext = NULL;
     PMG_CALL(pmg_dev_alloc((void **)&Bnext, sizeof(double) * (size_t)Cc->ld * k));
-    PMG_HIP(hipMemset(Bnext, 0, sizeof(double) * (size_t)Cc->ld * k));
+    PMG_CALL(pmg_dev_zero(Bnext, sizeof(double) * (size_t)Cc->ld * k));
     for (int c = 0; c < k; ++c) PMG_CALL(mg_restrict(h, l, Bcur + (size_t)Lv->ld * c, Bnext + (size_t)Cc->ld * c, NULL)); /* B_{l-1} = P_l^T B_l */
     PMG_HIP(hipDeviceSynchronize());
     pmg_dev_free(Bcur);
@@ -1458,9 +1458,9 @@ static pmg_status mgmc_setup_stencil(pmg_mgmc h, const st27_table *tab)
     PMG_CALL(pmg_dev_alloc((void **)&Lv->b, sizeof(double) * (size_t)Lv->ld));
     PMG_CALL(pmg_dev_alloc((void **)&Lv->x, sizeof(double) * (size_t)Lv->ld));
     PMG_CALL(pmg_dev_alloc((void **)&Lv->r, sizeof(double) * (size_t)Lv->ld));
-    PMG_HIP(hipMemset(Lv->b, 0, sizeof(double) * (size_t)Lv->ld));
-    PMG_HIP(hipMemset(Lv->x, 0, sizeof(double) * (size_t)Lv->ld));
-    PMG_HIP(hipMemset(Lv->r, 0, sizeof(double) * (size_t)Lv->ld));
+    PMG_CALL(pmg_dev_zero(Lv->b, sizeof(double) * (size_t)Lv->ld));
+    PMG_CALL(pmg_dev_zero(Lv->x, sizeof(double) * (size_t)Lv->ld));
+    PMG_CALL(pmg_dev_zero(Lv->r, sizeof(double) * (size_t)Lv->ld));
     if (st27_use_pair(Lv) || st27_use_pair_slab(Lv)) PMG_CALL(pmg_dev_alloc((void **)&Lv->x2, sizeof(double) * (size_t)Lv->ld)); /* zero-filled: the ghost planes stay zero */
     if (l >= 1 && Lv->is_grid && Lv->distributed && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused && (!h->lrc_k || (Lv->lrc && h->lv[l - 1].lrc)) && !(getenv("PMG_GRID_FUSED_RR_SLAB") && !atoi(getenv("PMG_GRID_FUSED_RR_SLAB")))) {
       /* the fused residual + restriction on a z-slab: every rank needs two planes (it hands its second and second-to-last
@@ -1490,16 +1490,16 @@ static pmg_status mgmc_setup_stencil(pmg_mgmc h, const st27_table *tab)
         PMG_CALL(pmg_grid_halo_plane(Lv->g, 0, 0, &own, &ghost, &np));
         PMG_CALL(pmg_dev_alloc((void **)&Lv->y2lo, sizeof(double) * 2 * (size_t)np));
         PMG_CALL(pmg_dev_alloc((void **)&Lv->y2hi, sizeof(double) * 2 * (size_t)np));
-        PMG_HIP(hipMemset(Lv->y2lo, 0, sizeof(double) * 2 * (size_t)np));
-        PMG_HIP(hipMemset(Lv->y2hi, 0, sizeof(double) * 2 * (size_t)np));
+        PMG_CALL(pmg_dev_zero(Lv->y2lo, sizeof(double) * 2 * (size_t)np));
+        PMG_CALL(pmg_dev_zero(Lv->y2hi, sizeof(double) * 2 * (size_t)np));
         Lv->rr_slab = 1;
       }
     }
   }
   PMG_CALL(pmg_dev_alloc((void **)&h->y_lay, sizeof(double) * (size_t)F->ld));
   PMG_CALL(pmg_dev_alloc((void **)&h->b_lay, sizeof(double) * (size_t)F->ld));
-  PMG_HIP(hipMemset(h->y_lay, 0, sizeof(double) * (size_t)F->ld));
-  PMG_HIP(hipMemset(h->b_lay, 0, sizeof(double) * (size_t)F->ld));
+  PMG_CALL(pmg_dev_zero(h->y_lay, sizeof(double) * (size_t)F->ld));
+  PMG_CALL(pmg_dev_zero(h->b_lay, sizeof(double) * (size_t)F->ld));
   h->is_setup = 1;
   return PMG_SUCCESS;
 }
