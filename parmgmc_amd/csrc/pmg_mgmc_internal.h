@@ -1,0 +1,165 @@
+/* What the translation units of the MGMC sampler share (C11): the handle, its levels, the host CSR type of the set-up and
+ * the few functions that cross files.
+ *   pmg_hier_host.c    pure host sparse tools of the set-up (no device call: they also run under the host sanitizer program)
+ *   pmg_mgmc_setup.c   handle construction, setters, the three set-up routines, getters of set-up data, destroy
+ *   pmg_mgmc.c         the V-cycle, its byte model and pmg_mgmc_sample
+ *   pmg_mgmc_chains.c  the multi-chain cycle
+ *   pmg_mgmc_level.c   single-kernel entry points of one level (diagnostics)
+ * Everything declared here is internal to the library: PMG_HIDDEN keeps it out of the exported symbols. */
+#ifndef PMG_MGMC_INTERNAL_H
+#define PMG_MGMC_INTERNAL_H
+#include "pmg_internal.h"
+
+#define PMG_HIDDEN __attribute__((visibility("hidden")))
+
+/* host CSR, natural numbering, columns ascending; a zeroed one is empty */
+typedef struct {
+  int32_t  nr, nc;
+  int32_t *rp, *ci;
+  double  *v;
+} hcsr;
+
+typedef struct {
+  int32_t   nx, ny, nz, n; /* global extents */
+  int32_t   kz0, nzl;      /* owned planes (0, nz on a single device and on replicated levels) */
+  int       padded;        /* plane-padded natural layout (class-stencil levels, Cholesky level): element (i,j,k) at off + i + nx (j + ny (k - kz0)) */
+  int64_t   off;           /* = nx*ny when padded */
+  int       distributed;   /* z-slab level of a multi-device hierarchy */
+  int       is_grid;
+  pmg_grid  g;
+  pmg_mcsor mc;
+  int64_t   ld;
+  double   *b, *x, *r;
+  int       x_zeroed; /* the restriction kernel has set the zero guess already */
+  int       x_unset; /* the iterate is zero but the memset was skipped: the next out-of-place sweep starts from NULL */
+  double   *y2lo, *y2hi; /* z-slab grid level: the iterate's planes kz0 - 2 and kz0 + nz + 1 (colour 0 plane, colour 1 plane) for the fused residual + restriction */
+  int       rr_slab;     /* ... which every rank can run (agreed from the slab cuts) */
+  double   *x2; /* second buffer of the out-of-place class-stencil sweep (single-device levels): x and x2 swap after every directional sweep */
+  /* transfers to the next coarser level, in layout numbering on the device */
+  int32_t  P_nrows, R_nrows;
+  int32_t *cpos_dev; /* grid level only: layout position of every point of the next coarser level */
+  /* class-stencil form of a structured Galerkin level (natural-order vectors) */
+  int       is_st27, nat_transfer; /* nat_transfer: this level and the next coarser one are both in padded natural order */
+  int       grid_transfer;         /* matrix-free Q1 transfers from this grid level (cpos_dev == NULL: padded natural coarse level) */
+  pmgk_st27 st;
+  double   *st_coef, *st_idiag, *st_sqrtd, *st_sqrtd_scaled;
+  pmg_lrc   lrc; /* MATLRC update of a class-stencil level (grid / sliced-ELL levels keep theirs inside g / mc) */
+  int32_t *P_rowpos, *P_rowptr, *P_col, *R_rowpos, *R_rowptr, *R_col;
+  double  *P_val, *R_val;
+  /* optional host copies (natural numbering) for inspection */
+  hcsr A_host, P_host;
+  /* caller-supplied hierarchy (borrowed host CSR until set-up) */
+  hcsr A_user, P_user;
+  int32_t *A_rp_own, *A_ci_own, *P_rp_own, *P_ci_own; /* 32-bit copies of 64-bit PetscInt arrays, freed after set-up */
+  /* ROW BLOCK of a distributed hierarchy (pmg_mgmc_set_level_rowblock): A_user is this rank's rows in LOCAL numbering --
+     owned rows first, then one identity row per ghost (every row of another rank that this rank's operator, restriction
+     or the finer level's interpolation reads); the plan lists are host copies until set-up builds `dm` from them */
+  int           rb;
+  int32_t       rb_nowned, rb_ncolors;
+  int64_t       rb_row0;
+  int32_t      *rb_colors, *rb_send_idx, *rb_recv_src, *rb_recv_idx;
+  int64_t      *rb_send_ptr, *rb_recv_ptr, *rb_counts;
+  hcsr          R_user; /* rows of the restriction INTO the next coarser level that this rank owns there (borrowed) */
+  pmg_distmcsor dm;
+  int64_t       A_nnz, P_nnz; /* stored entries of a sliced-ELL level's operator / of its CSR interpolation (traffic accounting) */
+} mg_level;
+
+struct pmg_mgmc_s {
+  int       nlevels;
+  mg_level *lv; /* lv[0] = coarsest */
+  double    kappa, omega;
+  int       nu, scaled, sweep_type;
+  int       coarse_type, coarse_its; /* 0 = cholsampler, 1 = Gibbs sweeps */
+  int       keep_host, is_setup, user_hier;
+  int       no_fused;        /* 1: residual and restriction as two kernels everywhere (pmg_mgmc_set_fused_transfers(mg, 0)) */
+  int       correction_form; /* 1: w = b - A y, y += MG(w) literally (src/pc_gamgmc.c:253-256); 0: the same cycle run in place on (b, y) */
+  pmg_chol  chol;
+  double   *y_lay, *b_lay;
+  /* MATLRC fine operator A + B S B^T (host copies until set-up; src/pc_gamgmc.c:157-196) */
+  int32_t   lrc_k;
+  double   *lrc_B, *lrc_S;
+  int       aij_coloring; /* rule of the AIJ levels (pmg_mgmc_set_coloring); PMG_COLORING_GREEDY = 0 */
+  double   *eta_batch; /* device: the low-rank noise terms of one cycle, drawn together (mg_draw_lowrank_noise) */
+  int       eta_batch_mode; /* 0: not asked yet, 1: on, -1: PMG_LRC_BATCH=0 when this sampler ran its first cycle */
+  int       own_grid; /* the fine grid operator was created here (not handed in with a slab) */
+  /* multi-device: z-slabs of the fine grid, one rank per device (borrowed dist object); cuts[l*(nranks+1) + r] =
+     first plane of rank r on level l */
+  pmg_dist  dist;
+  int32_t   rank, nranks;
+  int32_t  *cuts;
+  int32_t   n_io; /* length of the caller's fine-level vectors (the owned planes) */
+  /* row-block distributed caller-supplied hierarchy: transport (borrowed) and the row blocks of the replicated coarsest level */
+  pmg_dist  rb_dist;
+  int64_t  *rb_c0_starts; /* row blocks of the highest REPLICATED level (rb_fold - 1): who restricts which of its rows */
+  int       rb_fold;      /* lowest row-block level; the levels below are replicated on every rank */
+  int32_t  *rb_fold_pos, *rb_fold_iota; /* device: layout position of natural row q of level rb_fold - 1, and 0, 1, 2, ... */
+  double   *rb_fold_buf;                /* device: that level's vector in natural order (the all-gather buffer) */
+  /* multi-chain workspace (pmg_mgmc_sample_chains): allocated on first use, grows with the chain count */
+  int32_t    ch_cap;
+  double   **ch_b, **ch_x, **ch_r; /* [nlevels]: level vectors of ld x ch_cap doubles, chain fastest */
+  double    *ch_Y, *ch_bs;       /* the chains' iterate and the shared right-hand side in the finest level's layout */
+  double    *ch_xi, *ch_v;       /* exact coarse sampler: noise and L^-1 b + xi, n_0 x ch_cap */
+  pmg_keybuf ch_keys;            /* level_seed(seeds[c], l) at l * C + c */
+  double    *ch_B;               /* one right-hand side per chain in the finest level's layout (pmg_mgmc_sample_chains_rhs), ld x ch_B_cap */
+  int32_t    ch_B_cap;
+};
+
+typedef struct {
+  double coef[27 * 27];
+  int    have[27];
+} st27_table;
+
+#define MG_DRAWS_PER_SAMPLE 64u
+
+/* row generator: either a stored CSR or the matrix-free 7-point operator of src/problems.c:14-75 */
+typedef struct {
+  const hcsr *A;
+  int32_t     nx, ny, nz;
+  double      kappa, h2, diag[8];
+} rowsrc;
+
+/* *to takes over *from's arrays */
+static inline void hcsr_move(hcsr *to, hcsr *from)
+{
+  *to = *from;
+  memset(from, 0, sizeof *from);
+}
+
+/* per-level noise seed: levels draw from independent streams */
+static inline uint64_t level_seed(uint64_t seed, int level) { return seed + 0x9E3779B97F4A7C15ull * (uint64_t)(level + 1); }
+
+static inline double level_rows(const mg_level *Lv) { /* owned unknowns: a z-slab's planes, a row block's rows */ return Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n); }
+
+static inline pmgk_st27_dims level_dims(const mg_level *Lv) { return (pmgk_st27_dims){Lv->nx, Lv->ny, Lv->nzl, Lv->kz0, Lv->nz}; }
+
+/* the low-rank update a level's sampler applies (held by the level, or by the grid object of a single-device grid level) */
+static inline pmg_lrc mg_level_lrc(const mg_level *Lv) { return Lv->lrc ? Lv->lrc : (Lv->is_grid ? pmg_grid_lrc(Lv->g) : NULL); }
+
+/* ---- pmg_hier_host.c: host memory only.  A function that fails leaves its output matrix partly allocated: it stays the
+   caller's to release with pmg_hcsr_free, which accepts that state. */
+PMG_HIDDEN void       pmg_hcsr_free(hcsr *m);
+PMG_HIDDEN pmg_status pmg_hcsr_dup(const hcsr *A, hcsr *out);
+PMG_HIDDEN pmg_status pmg_hcsr_transpose(const hcsr *A, hcsr *T);
+PMG_HIDDEN pmg_status pmg_hier_q1_interp(const int32_t nf[3], const int32_t nc[3], hcsr *P);
+PMG_HIDDEN void       pmg_hier_laplace_rows(int32_t nx, int32_t ny, int32_t nz, double kappa, double h2, rowsrc *s);
+PMG_HIDDEN pmg_status pmg_hier_galerkin_rap(const rowsrc *A, int maxrow, const hcsr *P, const hcsr *R, hcsr *Cm);
+PMG_HIDDEN pmg_status pmg_hier_restrict_B(const hcsr *R, int32_t k, int32_t nf, const double *Bf, double **Bc_out);
+PMG_HIDDEN int        pmg_hier_st27_extract(int nx, int ny, int nz, const hcsr *A, double *coef /* [27*27] */, int *have /* [27] */);
+PMG_HIDDEN pmg_status pmg_hier_st27_to_csr(int nx, int ny, int nz, const st27_table *t, hcsr *A);
+PMG_HIDDEN pmg_status pmg_hier_stencil_tables(int nlevels, const int32_t (*dims)[3] /* [nlevels], 0 = coarsest */, double kappa, double h2, st27_table *tab /* [nlevels-1] */, int *ok);
+PMG_HIDDEN void       pmg_hier_parity_colouring(int32_t nx, int32_t ny, int32_t nz, int32_t *col /* [nx*ny*nz] */);
+
+/* ---- pmg_mgmc.c: the pieces of the cycle that the set-up (low-rank blocks restricted with the cycle's own kernels) and
+   the level diagnostics run too */
+PMG_HIDDEN int        pmg_mgmc_i_st27_out_of_place(const mg_level *Lv); /* the level's own iterate is swept out of place, into Lv->x2 */
+PMG_HIDDEN int        pmg_mgmc_i_level_wants_x2(const mg_level *Lv);    /* the set-up gives the level a second iterate buffer */
+PMG_HIDDEN pmg_status pmg_mgmc_i_halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stream);
+PMG_HIDDEN pmg_status pmg_mgmc_i_rb_fold_allgather(pmg_mgmc h, double *v, void *stream);
+PMG_HIDDEN pmg_status pmg_mgmc_i_level_residual(pmg_mgmc h, int l, const double *b, const double *x, double *r, void *stream);
+PMG_HIDDEN pmg_status pmg_mgmc_i_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coarse, void *stream);
+PMG_HIDDEN pmg_status pmg_mgmc_i_prolong_add(pmg_mgmc h, int l, const double *e_coarse, double *x_fine, int only_color, void *stream);
+/* ---- pmg_mgmc_chains.c, pmg_mgmc_level.c */
+PMG_HIDDEN void       pmg_mgmc_i_free_chains(pmg_mgmc h);
+PMG_HIDDEN pmg_status pmg_mgmc_i_level_checked(pmg_mgmc h, int32_t level, int need_coarser, mg_level **Lv);
+
+#endif

@@ -1,6 +1,7 @@
 /* AddressSanitizer + UndefinedBehaviorSanitizer run of the host-side C that needs no GPU: the CPU oracle (every orc_*
  * entry point on small cases, incl. the sampled-row functions the full-size parity tests rely on) and the pure-host parts
- * of libparmgmc_hip (index narrowing, chain diagnostics, observation matrices, the PCPARSOR data-flow builder).  Built
+ * of libparmgmc_hip (index narrowing, chain diagnostics, observation matrices, the PCPARSOR data-flow builder, the sparse
+ * tools of the MGMC set-up).  Built
  * and run by tests/test_sanitize_host.py with gcc -fsanitize=address,undefined; a finding aborts with a non-zero status.
  * (GPU AddressSanitizer is not available on the test pool: the kernels are covered by the parity tests only.) */
 #include <math.h>
@@ -204,6 +205,150 @@ static void *san_rank_create(void *arg)
   return NULL;
 }
 
+/* ---- pmg_hier_host.c: the host sparse tools of the MGMC set-up on the smallest grids where they can go wrong.  One chain of
+   grids, finest first: the first Galerkin product reads the matrix-free 7-point rows, the later ones the previous product's
+   CSR.  Per step: P rows sum to 1, R is P's exact transpose, the fused product against a dense triple product formed here,
+   the class-stencil table round trip, the parity colouring; from the second step on also the error path of a row that does
+   not fit.  tabs (may be NULL): the class tables per step. ------------------------------------------------------------- */
+#include "../../parmgmc_amd/csrc/pmg_mgmc_internal.h"
+#define HREQUIRE(c) \
+  do { \
+    if (!(c)) { \
+      fprintf(stderr, "host_san: check failed at line %d: %s\n", __LINE__, #c); \
+      return 1; \
+    } \
+  } while (0)
+
+static void san_dense(const hcsr *M, double *D) /* nr x nc row-major */
+{
+  memset(D, 0, sizeof(double) * (size_t)M->nr * (size_t)M->nc);
+  for (int32_t r = 0; r < M->nr; ++r)
+    for (int32_t q = M->rp[r]; q < M->rp[r + 1]; ++q) D[(size_t)r * M->nc + M->ci[q]] = M->v[q];
+}
+
+static int san_hier_chain(int nsteps, const int32_t (*dims)[3], double kappa, st27_table *tabs)
+{
+  const int32_t *f0 = dims[0];
+  const double   h2 = 1. / ((f0[0] - 1) * (f0[0] - 1));
+  rowsrc         src;
+  hcsr           Aprev;
+  pmg_hier_laplace_rows(f0[0], f0[1], f0[2], kappa, h2, &src);
+  memset(&Aprev, 0, sizeof Aprev);
+  for (int st = 0; st < nsteps; ++st) {
+    const int32_t *df = dims[st], *dc = dims[st + 1];
+    const int32_t  nf = df[0] * df[1] * df[2], nc = dc[0] * dc[1] * dc[2];
+    hcsr           P, R, Ac, B, D;
+    memset(&P, 0, sizeof P), memset(&R, 0, sizeof R), memset(&Ac, 0, sizeof Ac), memset(&B, 0, sizeof B), memset(&D, 0, sizeof D);
+    HREQUIRE(pmg_hier_q1_interp(df, dc, &P) == 0 && P.nr == nf && P.nc == nc);
+    for (int32_t r = 0; r < nf; ++r) { /* weights are 1, 1/2, 1/4, 1/8: the row sums are exact */
+      double sum = 0.0;
+      for (int32_t q = P.rp[r]; q < P.rp[r + 1]; ++q) sum += P.v[q];
+      HREQUIRE(sum == 1.0);
+      for (int32_t q = P.rp[r] + 1; q < P.rp[r + 1]; ++q) HREQUIRE(P.ci[q - 1] < P.ci[q]);
+    }
+    HREQUIRE(pmg_hcsr_transpose(&P, &R) == 0 && R.nr == nc && R.nc == nf && R.rp[nc] == P.rp[nf]);
+    double *Pd = malloc(sizeof(double) * nf * nc), *Rd = malloc(sizeof(double) * nc * nf), *Ad = calloc((size_t)nf * nf, sizeof(double));
+    double *T = calloc((size_t)nf * nc, sizeof(double)), *Ta = calloc((size_t)nf * nc, sizeof(double)), *Cd = calloc((size_t)nc * nc, sizeof(double)), *Ca = calloc((size_t)nc * nc, sizeof(double));
+    san_dense(&P, Pd);
+    san_dense(&R, Rd);
+    for (int32_t r = 0; r < nf; ++r)
+      for (int32_t c = 0; c < nc; ++c) HREQUIRE(Rd[(size_t)c * nf + r] == Pd[(size_t)r * nc + c]);
+    for (int32_t r = 0; r < nc; ++r)
+      for (int32_t q = R.rp[r] + 1; q < R.rp[r + 1]; ++q) HREQUIRE(R.ci[q - 1] < R.ci[q]);
+    HREQUIRE(pmg_hcsr_dup(&P, &D) == 0 && D.nr == P.nr && D.nc == P.nc && !memcmp(D.rp, P.rp, sizeof(int32_t) * (nf + 1)) && !memcmp(D.ci, P.ci, sizeof(int32_t) * P.rp[nf]) && !memcmp(D.v, P.v, sizeof(double) * P.rp[nf]));
+    /* the fine operator, dense: the 7-point operator of src/problems.c restated (kappa^2 plus h2 per neighbour on the
+       diagonal, -h2 beside it), afterwards the product of the step before */
+    rowsrc s = src;
+    if (st == 0) {
+      for (int32_t k = 0; k < df[2]; ++k)
+        for (int32_t j = 0; j < df[1]; ++j)
+          for (int32_t i = 0; i < df[0]; ++i) {
+            const int32_t r = i + df[0] * (j + df[1] * k), nb[6] = {i > 0 ? r - 1 : -1, i < df[0] - 1 ? r + 1 : -1, j > 0 ? r - df[0] : -1, j < df[1] - 1 ? r + df[0] : -1, k > 0 ? r - df[0] * df[1] : -1, k < df[2] - 1 ? r + df[0] * df[1] : -1};
+            double        d = kappa * kappa;
+            for (int q = 0; q < 6; ++q)
+              if (nb[q] >= 0) d += h2, Ad[(size_t)r * nf + nb[q]] = -h2;
+            Ad[(size_t)r * nf + r] = d;
+          }
+    } else {
+      s.A = &Aprev;
+      HREQUIRE(Aprev.nr == nf);
+      san_dense(&Aprev, Ad);
+      /* a row of the 27-point operator does not fit 7 entries: an error, and nothing is left behind but the output */
+      HREQUIRE(pmg_hier_galerkin_rap(&s, 7, &P, &R, &B) == PMG_ERR_ARG_SIZ);
+      pmg_hcsr_free(&B);
+    }
+    HREQUIRE(pmg_hier_galerkin_rap(&s, st == 0 ? 7 : 64, &P, &R, &Ac) == 0 && Ac.nr == nc && Ac.nc == nc);
+    /* C = P^T (A P) dense, with |P|^T (|A| |P|) beside it.  Each entry of either product is a plain sum of at most 27 * 27
+       products of O(1) numbers, and the Q1 weights are powers of two, so only the additions round: the rounding errors of
+       729 terms accumulate like 27 * 2^-53 = 3e-15 of the absolute sum, and 1e-14 of it bounds the difference of the two */
+    for (int32_t i = 0; i < nf; ++i)
+      for (int32_t j = 0; j < nf; ++j) {
+        const double a = Ad[(size_t)i * nf + j];
+        if (a != 0.0)
+          for (int32_t c = 0; c < nc; ++c) T[(size_t)i * nc + c] += a * Pd[(size_t)j * nc + c], Ta[(size_t)i * nc + c] += fabs(a) * Pd[(size_t)j * nc + c];
+      }
+    for (int32_t I = 0; I < nc; ++I)
+      for (int32_t i = 0; i < nf; ++i) {
+        const double r = Rd[(size_t)I * nf + i];
+        if (r != 0.0)
+          for (int32_t c = 0; c < nc; ++c) Cd[(size_t)I * nc + c] += r * T[(size_t)i * nc + c], Ca[(size_t)I * nc + c] += r * Ta[(size_t)i * nc + c];
+      }
+    double *Gd = malloc(sizeof(double) * nc * nc);
+    san_dense(&Ac, Gd);
+    for (int32_t q = 0; q < nc * nc; ++q) HREQUIRE(fabs(Gd[q] - Cd[q]) <= 1e-14 * Ca[q]);
+    for (int32_t r = 0; r < nc; ++r)
+      for (int32_t q = Ac.rp[r] + 1; q < Ac.rp[r + 1]; ++q) HREQUIRE(Ac.ci[q - 1] < Ac.ci[q]);
+    /* class-stencil table and back: the same CSR, bit for bit */
+    st27_table t;
+    HREQUIRE(pmg_hier_st27_extract(dc[0], dc[1], dc[2], &Ac, t.coef, t.have) == 1);
+    if (tabs) tabs[st] = t;
+    HREQUIRE(pmg_hier_st27_to_csr(dc[0], dc[1], dc[2], &t, &B) == 0 && B.nr == nc && B.rp[nc] == Ac.rp[nc]);
+    HREQUIRE(!memcmp(B.rp, Ac.rp, sizeof(int32_t) * (nc + 1)) && !memcmp(B.ci, Ac.ci, sizeof(int32_t) * Ac.rp[nc]) && !memcmp(B.v, Ac.v, sizeof(double) * Ac.rp[nc]));
+    /* the parity colouring: consecutive colours from 0, no two coupled rows share one */
+    int32_t *col = malloc(sizeof(int32_t) * nc);
+    int      seen[8] = {0}, ncol = 0;
+    pmg_hier_parity_colouring(dc[0], dc[1], dc[2], col);
+    for (int32_t r = 0; r < nc; ++r) {
+      HREQUIRE(col[r] >= 0 && col[r] < 8);
+      seen[col[r]] = 1;
+      for (int32_t q = Ac.rp[r]; q < Ac.rp[r + 1]; ++q) HREQUIRE(Ac.ci[q] == r || col[Ac.ci[q]] != col[r]);
+    }
+    while (ncol < 8 && seen[ncol]) ++ncol;
+    for (int q = ncol; q < 8; ++q) HREQUIRE(!seen[q]);
+    /* B_c = P^T B_f on two columns against the dense transpose */
+    double *Bf = malloc(sizeof(double) * 2 * nf), *Bc = NULL;
+    for (int32_t q = 0; q < 2 * nf; ++q) Bf[q] = sin(0.3 + q);
+    HREQUIRE(pmg_hier_restrict_B(&R, 2, nf, Bf, &Bc) == 0);
+    for (int c = 0; c < 2; ++c)
+      for (int32_t I = 0; I < nc; ++I) {
+        double acc = 0.0, mag = 0.0;
+        for (int32_t i = 0; i < nf; ++i) acc += Rd[(size_t)I * nf + i] * Bf[(size_t)nf * c + i], mag += Rd[(size_t)I * nf + i] * fabs(Bf[(size_t)nf * c + i]);
+        HREQUIRE(fabs(Bc[(size_t)nc * c + I] - acc) <= 1e-14 * mag);
+      }
+    free(Bf), free(Bc), free(col), free(Gd), free(Pd), free(Rd), free(Ad), free(T), free(Ta), free(Cd), free(Ca);
+    pmg_hcsr_free(&P), pmg_hcsr_free(&R), pmg_hcsr_free(&B), pmg_hcsr_free(&D), pmg_hcsr_free(&Aprev);
+    hcsr_move(&Aprev, &Ac);
+  }
+  pmg_hcsr_free(&Aprev);
+  return 0;
+}
+
+static int san_hier(void)
+{
+  const int32_t g555[3][3] = {{5, 5, 5}, {3, 3, 3}, {2, 2, 2}}, g531[2][3] = {{5, 3, 1}, {3, 2, 1}}, g953[2][3] = {{9, 5, 3}, {5, 3, 2}};
+  const double  kappa = 1.3; /* kappa^2 is no dyadic number: the diagonal sums round */
+  st27_table    chain[2], proxy[2];
+  int           ok = 0;
+  HREQUIRE(san_hier_chain(2, g555, kappa, chain) == 0);
+  HREQUIRE(san_hier_chain(1, g531, kappa, NULL) == 0);
+  HREQUIRE(san_hier_chain(1, g953, kappa, NULL) == 0);
+  /* the proxy hierarchy of 5^3 with 3 levels is the hierarchy itself (levels coarsest first): the same tables */
+  const int32_t lv555[3][3] = {{2, 2, 2}, {3, 3, 3}, {5, 5, 5}};
+  HREQUIRE(pmg_hier_stencil_tables(3, lv555, kappa, 1. / 16, proxy, &ok) == 0 && ok == 1);
+  HREQUIRE(!memcmp(proxy[1].coef, chain[0].coef, sizeof proxy[1].coef) && !memcmp(proxy[0].coef, chain[1].coef, sizeof proxy[0].coef));
+  return 0;
+}
+
 #define REQUIRE(c) \
   do { \
     if (!(c)) { \
@@ -343,6 +488,7 @@ int main(void)
     REQUIRE(mci[0] == 3 && mci[2] == 1 && mci[3] == 3 && mci[5] == 0 && mci[6] == 6);
     REQUIRE(pmg_rowblock_merge_mpiaij(2, 3, ad_rp, ad_ci, ad_v, ao_rp, ao_ci, ao_v, ga, 48, 0, mrp, mci, mv) == PMG_ERR_ARG_OUTOFRANGE);
   }
+  REQUIRE(san_hier() == 0);
   printf("host_san ok\n");
   return 0;
 }
