@@ -445,15 +445,19 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc mg, double *total, double *pe
    from pmg_mgmc_create_hierarchy on one device whose levels are all sliced-ELL, with either coarse sampler and either
    correction form.  Layout, seeds, counters and bit identity as for pmg_mcsor_sample_chains: chain c uses seeds_host[c] and
    per level level_seed(seeds_host[c], l), sample s the counters [64 s, 64 s + 64).  The callback follows
-   pmg_sample_callback's rules with all chains' samples (Y_nat_dev, n x nchains, chain fastest).  PMG_ERR_SUP: DMDA
-   hierarchies (pmg_mgmc_create_dmda*), row-block hierarchies, a low-rank update; other errors as pmg_mcsor_sample_chains. */
+   pmg_sample_callback's rules with all chains' samples (Y_nat_dev, n x nchains, chain fastest).  A set-up hierarchy that carries
+   pmg_mgmc_set_lowrank (MATLRC levels, either storage form of the update) is sampled as pmg_mgmc_sample samples it: the noise
+   term, the repair and the residual's low-rank term on every level, the exact coarse sampler on the explicit sum; b is never
+   written.  PMG_ERR_SUP: DMDA hierarchies (pmg_mgmc_create_dmda*), row-block hierarchies, a low-rank update on a handle that
+   is not set up yet (whether its levels carry it is known after set-up only); other errors as pmg_mcsor_sample_chains. */
 typedef int (*pmg_chains_callback)(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
 pmg_status pmg_mgmc_sample_chains(pmg_mgmc mg, int32_t nchains, const uint64_t *seeds_host, const double *b_nat_dev, double *Y_nat_dev, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
 /* the same with ONE RIGHT-HAND SIDE PER CHAIN: B_nat_dev is n x nchains, chain fastest; column c equals pmg_mgmc_sample with
    b = B[:, c] -- the prior sampler under pmg_woodbury_noisy_rhs_chains.  Checks and errors as pmg_mgmc_sample_chains. */
 pmg_status pmg_mgmc_sample_chains_rhs(pmg_mgmc mg, int32_t nchains, const uint64_t *seeds_host, const double *B_nat_dev, double *Y_nat_dev, int32_t its, int guesszero, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
 /* algorithmic bytes of ONE V-cycle advancing all C chains (the chains analogue of pmg_mgmc_get_algorithmic_bytes): shared
-   operands (matrices, idiag, sqrtdiag, the shared b, P, W) counted once, iterates and per-chain right-hand sides C times */
+   operands (matrices, idiag, sqrtdiag, the shared b, P, W, the low-rank factors and their rows) counted once, iterates, k-vectors
+   and per-chain right-hand sides C times; the formula is listed at the definition (pmg_mgmc_chains.c) and in DESIGN.md 11.1 */
 pmg_status pmg_mgmc_get_algorithmic_bytes_chains(pmg_mgmc mg, int32_t nchains, double *total, double *per_level_host);
 /* Diagnostics: ONE kernel of the V-cycle on caller-supplied device vectors in the level's own layout (single device).
    They exist for the parity tests at 257^3 / 513^3, where a whole oracle cycle is out of reach: the tests run one
@@ -474,6 +478,9 @@ pmg_status pmg_mgmc_level_prolong_add(pmg_mgmc mg, int32_t level, const double *
    ns layout positions of the support rows, ascending, and the ns x k column-major blocks of B_l (= P^T ... P^T B,
    src/pc_gamgmc.c:177-178), Bb forward and Bb backward (MCSORBuildLRCCorrection, src/mc_sor.c:480-544).  NULL arrays query k, ns. */
 pmg_status pmg_mgmc_level_lowrank_factors(pmg_mgmc mg, int32_t level, int32_t *k, int64_t *ns, int64_t *rows_host, double *B_host, double *Bb_fwd_host, double *Bb_bwd_host);
+/* the sizes alone, on every kind of level (also the sliced-ELL levels of a caller-supplied hierarchy): the rank and the rows the
+   level's low-rank passes run over -- the support rows of the row-compact form, every row of the dense form (*dense = 1) */
+pmg_status pmg_mgmc_level_lowrank_sizes(pmg_mgmc mg, int32_t level, int32_t *k, int64_t *rows, int *dense);
 /* y -= Bb (B^T y), MCSORPostSOR_LRC (src/mc_sor.c:101-112), on a vector in the level's layout */
 pmg_status pmg_mgmc_level_lowrank_post(pmg_mgmc mg, int32_t level, int backward, double *y_lvl, void *stream);
 /* restricted = 0: out (level layout) -= B_l (S B_l^T x); 1: out (layout of level-1) -= B_{l-1} (S B_l^T x) */

@@ -16,6 +16,13 @@
 //   block sums (lrc_reduce_kernel): virtual lane l adds blocks l, l + 64, ... from 0.0, then the same tree, then the scale.
 //   updates (lrc_axpy_cols_kernel, lrc_axpy_rows_kernel): fma chain over the columns from 0.0, out = in + sign * s.
 //   noise (fill_normal_rows_kernel<true>): pair q of the row stream (key, sweep) gives entries 2q and 2q + 1, times sqrt(S).
+//
+// The V-cycle of the chains (pmg_mgmc_chains.c) runs these in fewer launches, same sums:
+//   lrc_noise_batch_chains_kernel  every noise term of one cycle (level, draw, column, chain) from the cycle's key table;
+//   lrc_axpy_chains_kernel         with save_out the noise term goes onto a right-hand side IN PLACE and the old entries are
+//                                  kept (nr x C); with restore they go back in the repair's update pass over the same rows;
+//   lrc_small_chains_kernel        a support of one block of rows: B^T y, its (one-block) reduction with the scale and the
+//                                  update that consumes it by ONE workgroup per chunk of 64 chains, the k x 64 sums in LDS.
 #include <hip/hip_runtime.h>
 #include "pmg_kernels.h"
 #define PMG_RNG_LITERALS // as in kernels_lrc.hip
@@ -83,18 +90,17 @@ __device__ __noinline__ kvals btx_slot(int slot, int64_t q0, int64_t n, const in
   return s;
 }
 
-// partial[((blk * k) + j) * C + c] = block blk's sum of M[q + ldm j] * Y[row(q) * C + c] over its 256 * R rows q < n, row(q) =
-// rows[q] (compact form) or q (dense form).  Block (blockIdx.x, blockIdx.y = chunk of 64 chains), 256 threads; LPRL =
-// log2 lanes per chain group.
-template <int R, bool ROWS, int LPRL>
-__global__ __launch_bounds__(256) void lrc_btx_chains_kernel(int64_t n, const int64_t *__restrict__ rows, int k, const double *__restrict__ M, int64_t ldm, const double *__restrict__ Y, int32_t C, double *__restrict__ partial)
+// The sums of block blk of B^T y for the chunk of 64 chains blockIdx.y: store(j, cc, sum) is called once per column j < k and
+// chain blockIdx.y * 64 + cc < C with block blk's sum of M[q + ldm j] * Y[row(q) * C + c] over its 256 * R rows q < n, row(q) =
+// rows[q] (compact form) or q (dense form).  256 threads; LPRL = log2 lanes per chain group.  Ends behind a barrier.
+template <int R, bool ROWS, int LPRL, class Store>
+__device__ __forceinline__ void btx_block(int64_t blk, int64_t n, const int64_t *__restrict__ rows, int k, const double *__restrict__ M, int64_t ldm, const double *__restrict__ Y, int32_t C, double (&red)[4][KB][64], const Store &store)
 {
   constexpr int LPR = 1 << LPRL, G = 64 / LPR; // lanes per group, groups per wavefront; a group sums LPR leaves
-  __shared__ double red[4][KB][64];
   const int     lane = threadIdx.x & 63, wv = threadIdx.x >> 6, g = lane >> LPRL, cl = lane & (LPR - 1);
   const int     c    = blockIdx.y * 64 + cl;
   const bool    live = c < C;
-  const int64_t q0   = (int64_t)blockIdx.x * (256 * R) + 64 * wv;
+  const int64_t q0   = blk * (256 * R) + 64 * wv;
   for (int j0 = 0; j0 < k; j0 += KB) {
     auto leaf = [&](int slot, double (&s)[KB]) {
       const kvals r = btx_slot<R, ROWS>(slot, q0, n, rows, k, j0, M, ldm, Y, C, c, live);
@@ -112,10 +118,44 @@ __global__ __launch_bounds__(256) void lrc_btx_chains_kernel(int64_t n, const in
       for (int j = 0; j < KB; ++j) red[wv][j][cl] = v[j];
     __syncthreads();
     if (threadIdx.x < KB * LPR) {
-      const int j = threadIdx.x >> LPRL, cc = threadIdx.x & (LPR - 1), ch = blockIdx.y * 64 + cc;
-      if (j0 + j < k && ch < C) partial[((int64_t)blockIdx.x * k + j0 + j) * C + ch] = (red[0][j][cc] + red[1][j][cc]) + (red[2][j][cc] + red[3][j][cc]);
+      const int j = threadIdx.x >> LPRL, cc = threadIdx.x & (LPR - 1);
+      if (j0 + j < k && (int)blockIdx.y * 64 + cc < C) store(j0 + j, cc, (red[0][j][cc] + red[1][j][cc]) + (red[2][j][cc] + red[3][j][cc]));
     }
     __syncthreads();
+  }
+}
+
+// partial[((blk * k) + j) * C + c] = block blk's sum (btx_block).  Block (blockIdx.x, blockIdx.y = chunk of 64 chains)
+template <int R, bool ROWS, int LPRL>
+__global__ __launch_bounds__(256) void lrc_btx_chains_kernel(int64_t n, const int64_t *__restrict__ rows, int k, const double *__restrict__ M, int64_t ldm, const double *__restrict__ Y, int32_t C, double *__restrict__ partial)
+{
+  __shared__ double red[4][KB][64];
+  btx_block<R, ROWS, LPRL>((int64_t)blockIdx.x, n, rows, k, M, ldm, Y, C, red, [&](int j, int cc, double v) { partial[((int64_t)blockIdx.x * k + j) * C + blockIdx.y * 64 + cc] = v; });
+}
+
+// One workgroup per chunk of 64 chains on a support of ONE block of rows (ns <= 256 * 4): w = scale o (Mc^T Y) as
+// lrc_btx_chains_kernel + lrc_reduce_chains_kernel form it from a single block sum p (0.0 + p: the virtual lane's chain, the
+// other leaves of the tree add + 0.0, which changes nothing any more; then the scale), kept in LDS, and out[rows[q] * C + c] +=
+// sign * sum_j M2[q + ns j] w[j][c] as lrc_axpy_chains_kernel (in = out).  out may be Y: every read of Y is in front of the
+// barriers, and a chunk touches its own chains only.  restore: rdst[rows[q] * C + c] = restore[q * C + c] in the same pass.
+template <int LPRL>
+__global__ __launch_bounds__(256) void lrc_small_chains_kernel(int64_t ns, const int64_t *__restrict__ rows, int k, const double *__restrict__ Mc, const double *Y, int32_t C, const double *__restrict__ scale, const double *__restrict__ M2, double sign, double *out, const double *__restrict__ restore, double *rdst)
+{
+  constexpr int LPR = 1 << LPRL;
+  __shared__ double red[4][KB][64];
+  __shared__ double w[64][64]; // [column][chain of the chunk]
+  btx_block<4, true, LPRL>(0, ns, rows, k, Mc, ns, Y, C, red, [&](int j, int cc, double p) {
+    const double a = 0.0 + p;
+    w[j][cc]       = scale ? scale[j] * a : a;
+  });
+  const int cc = threadIdx.x & (LPR - 1), c = blockIdx.y * 64 + cc;
+  if (c >= C) return;
+  for (int64_t q = threadIdx.x >> LPRL; q < ns; q += 256 >> LPRL) {
+    double s = 0.0;
+    for (int j = 0; j < k; ++j) s = fma(M2[q + ns * j], w[j][cc], s);
+    const int64_t o = rows[q] * C + c;
+    out[o]          = out[o] + sign * s;
+    if (restore) rdst[o] = restore[q * C + c];
   }
 }
 
@@ -138,9 +178,10 @@ __global__ __launch_bounds__(256) void lrc_reduce_chains_kernel(int nb, int k, i
 }
 
 // out[row(q) * C + c] = in[row(q) (* C + c)] + sign * sum_j M[q + ldm j] coef[j * C + c], q < nr; row(q) = rows[q] or q.
-// in may be out (the repair); in_cs = 0: one vector shared by the chains.
+// in may be out (the repair); in_cs = 0: one vector shared by the chains.  save_out != NULL: save_out[q * C + c] = the value of
+// in that was read (the noise term in place); restore != NULL: rdst[row(q) * C + c] = restore[q * C + c] (it goes back).
 template <bool ROWS>
-__global__ __launch_bounds__(256) void lrc_axpy_chains_kernel(int64_t nr, const int64_t *__restrict__ rows, int k, const double *__restrict__ M, int64_t ldm, const double *__restrict__ coef, double sign, const double *in, int in_cs, double *out, int lpr_log2, int32_t C)
+__global__ __launch_bounds__(256) void lrc_axpy_chains_kernel(int64_t nr, const int64_t *__restrict__ rows, int k, const double *__restrict__ M, int64_t ldm, const double *__restrict__ coef, double sign, const double *in, int in_cs, double *out, int lpr_log2, int32_t C, double *__restrict__ save_out, const double *__restrict__ restore, double *rdst)
 {
   const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
   const int64_t q = t >> lpr_log2;
@@ -150,7 +191,10 @@ __global__ __launch_bounds__(256) void lrc_axpy_chains_kernel(int64_t nr, const 
   double        s = 0.0;
   for (int j = 0; j < k; ++j) s = fma(M[q + ldm * j], coef[(int64_t)j * C + c], s);
   const int64_t o = r * C + c;
-  out[o]          = in[in_cs ? o : r] + sign * s;
+  const double  v = in[in_cs ? o : r];
+  if (save_out) save_out[q * C + c] = v;
+  out[o] = v + sign * s;
+  if (restore) rdst[o] = restore[q * C + c];
 }
 
 // eta[j * C + c] = entry j of the row stream (keys[c] + tag, sweep) times sqrtS[j], j < k
@@ -168,6 +212,28 @@ __global__ __launch_bounds__(256) void lrc_noise_chains_kernel(int k, int lpr_lo
   pmg::normal_pair((uint32_t)q, 0u, (uint32_t)sweep, (uint32_t)(sweep >> 32), (uint32_t)key, (uint32_t)(key >> 32), s_logtab, z0, z1);
   eta[2 * q * C + c] = z0 * sqrtS[2 * q];
   if (2 * q + 1 < k) eta[(2 * q + 1) * C + c] = z1 * sqrtS[2 * q + 1];
+}
+
+// The noise terms of one cycle: slot s = plan.first[i] + d is draw d of entry i (a level with an update), eta[(s * k + j) * C + c]
+// = entry j of the row stream (keys[plan.level[i] * C + c] + tag, plan.ctr0[i] + d) times sqrtS[j]: lrc_noise_chains_kernel's
+// numbers for that level's keys and that counter.  blockIdx.z = slot.
+__global__ __launch_bounds__(256) void lrc_noise_batch_chains_kernel(int k, int lpr_log2, int32_t C, const uint64_t *__restrict__ keys, uint64_t tag, pmgk_lrc_noise_plan plan, const double *__restrict__ sqrtS, double *__restrict__ eta)
+{
+  __shared__ pmg::LogTabEntry s_logtab[PMG_LOGTAB_SIZE];
+  pmg::load_log_table(s_logtab);
+  __syncthreads();
+  const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const int64_t q = t >> lpr_log2;
+  const int     c = blockIdx.y * 64 + (int)(t & ((1 << lpr_log2) - 1)), slot = blockIdx.z;
+  if (2 * q >= k || c >= C) return;
+  int i = 0;
+  while (i + 1 < plan.n && plan.first[i + 1] <= slot) ++i;
+  const uint64_t key = keys[(int64_t)plan.level[i] * C + c] + tag, sweep = plan.ctr0[i] + (uint64_t)(slot - plan.first[i]);
+  double         z0, z1;
+  pmg::normal_pair((uint32_t)q, 0u, (uint32_t)sweep, (uint32_t)(sweep >> 32), (uint32_t)key, (uint32_t)(key >> 32), s_logtab, z0, z1);
+  double *e          = eta + (int64_t)slot * k * C;
+  e[2 * q * C + c] = z0 * sqrtS[2 * q];
+  if (2 * q + 1 < k) e[(2 * q + 1) * C + c] = z1 * sqrtS[2 * q + 1];
 }
 
 inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : 1; }
@@ -208,13 +274,50 @@ extern "C" int pmgk_lrc_btx_chains(int64_t n, const int64_t *rows, int k, const 
   return launch_status();
 }
 
-extern "C" int pmgk_lrc_axpy_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, void *stream)
+/* pmgk_lrc_axpy_chains that also keeps what it read (save_out, nr x C) and / or puts saved entries back (rdst at the rows = restore) */
+extern "C" int pmgk_lrc_axpy_save_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, double *save_out, const double *restore, double *rdst, void *stream)
 {
   if (nr <= 0 || nchains <= 0) return 0;
   const int  lprl = lpr_log2_of(nchains);
   const dim3 grid((unsigned)((nr * (1 << lprl) + 255) / 256), chunks_of(nchains));
-  if (rows) hipLaunchKernelGGL((lrc_axpy_chains_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, nr, rows, k, M, ldm, coef, sign, in, in_cs, out, lprl, nchains);
-  else hipLaunchKernelGGL((lrc_axpy_chains_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, nr, rows, k, M, ldm, coef, sign, in, in_cs, out, lprl, nchains);
+  if (rows) hipLaunchKernelGGL((lrc_axpy_chains_kernel<true>), grid, dim3(256), 0, (hipStream_t)stream, nr, rows, k, M, ldm, coef, sign, in, in_cs, out, lprl, nchains, save_out, restore, rdst);
+  else hipLaunchKernelGGL((lrc_axpy_chains_kernel<false>), grid, dim3(256), 0, (hipStream_t)stream, nr, rows, k, M, ldm, coef, sign, in, in_cs, out, lprl, nchains, save_out, restore, rdst);
+  return launch_status();
+}
+
+extern "C" int pmgk_lrc_axpy_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, void *stream)
+{
+  return pmgk_lrc_axpy_save_chains(nr, rows, k, M, ldm, coef, sign, in, in_cs, out, nchains, NULL, NULL, NULL, stream);
+}
+
+/* one launch for out[rows] += sign * M2 (scale o (Mc^T Y)) per chain on a support of one block of rows (ns <= pmgk_lrc_rows_per_block(),
+   Mc and M2 ns x k): the bits of pmgk_lrc_btx_chains + pmgk_lrc_axpy_chains.  out may be Y; restore as pmgk_lrc_axpy_save_chains */
+extern "C" int pmgk_lrc_small_chains(int64_t ns, const int64_t *rows, int k, const double *Mc, const double *Y, int32_t nchains, const double *scale, const double *M2, double sign, double *out, const double *restore, double *rdst, void *stream)
+{
+  if (ns <= 0 || k <= 0 || nchains <= 0) return 0;
+  if (k > 64 || !rows || ns > 256 * 4 || pmgk_lrc_rows_per_block() != 256 * 4) return 1;
+  const hipStream_t st = (hipStream_t)stream;
+  const dim3        grid(1, chunks_of(nchains));
+  switch (lpr_log2_of(nchains)) {
+  case 0: hipLaunchKernelGGL((lrc_small_chains_kernel<0>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  case 1: hipLaunchKernelGGL((lrc_small_chains_kernel<1>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  case 2: hipLaunchKernelGGL((lrc_small_chains_kernel<2>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  case 3: hipLaunchKernelGGL((lrc_small_chains_kernel<3>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  case 4: hipLaunchKernelGGL((lrc_small_chains_kernel<4>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  case 5: hipLaunchKernelGGL((lrc_small_chains_kernel<5>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  default: hipLaunchKernelGGL((lrc_small_chains_kernel<6>), grid, dim3(256), 0, st, ns, rows, k, Mc, Y, nchains, scale, M2, sign, out, restore, rdst); break;
+  }
+  return launch_status();
+}
+
+/* eta (nslots x k x C) = every noise term of the plan's slots in one launch (slot s at eta + s * k * C) */
+extern "C" int pmgk_lrc_noise_batch_chains(int nslots, int k, int32_t nchains, const uint64_t *keys, uint64_t tag, const pmgk_lrc_noise_plan *plan, const double *sqrtS, double *eta, void *stream)
+{
+  if (nslots <= 0 || k <= 0 || nchains <= 0) return 0;
+  if (nslots > 65535 || plan->n < 1 || plan->n > PMGK_LRC_NOISE_PLAN_MAX) return 1;
+  const int  lprl = lpr_log2_of(nchains);
+  const dim3 grid((unsigned)(((int64_t)(k + 1) / 2 * (1 << lprl) + 255) / 256), chunks_of(nchains), (unsigned)nslots);
+  hipLaunchKernelGGL(lrc_noise_batch_chains_kernel, grid, dim3(256), 0, (hipStream_t)stream, k, lprl, nchains, keys, tag, *plan, sqrtS, eta);
   return launch_status();
 }
 

@@ -73,6 +73,12 @@ void       pmg_lrc_destroy(pmg_lrc *l);
 /* the noise term and the repair on C chains (ld x C, chain fastest): pmg_lrc_rhs into out (b chain stride b_cs) / pmg_lrc_post per column */
 pmg_status pmg_lrc_rhs_chains(pmg_lrc l, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *b_lay, int b_cs, double *out_lay, void *stream);
 pmg_status pmg_lrc_post_chains(pmg_lrc l, int32_t nchains, int dir, double *Y_lay, void *stream);
+/* the forms of the chains V-cycle: the noise term (eta_dev k x C, drawn) IN PLACE on a right-hand side the cycle owns, the repair
+   that puts the entries under it back, the residual's term R -= B (S o (B^T X)); 1: one launch each for the last two */
+pmg_status pmg_lrc_rhs_inplace_chains(pmg_lrc l, int32_t nchains, const double *eta_dev, double *B_lay, void *stream);
+pmg_status pmg_lrc_post_restore_chains(pmg_lrc l, int32_t nchains, int dir, double *Y_lay, void *stream);
+pmg_status pmg_lrc_residual_sub_chains(pmg_lrc l, int32_t nchains, const double *X_lay, double *R_lay, void *stream);
+int        pmg_lrc_chains_fused(pmg_lrc l);
 pmg_status pmg_mcsor_set_idiag_by_division(pmg_mcsor mc, int on); /* PCPARSOR's idiag = omega / d */
 pmg_status pmg_mcsor_set_natural_order(pmg_mcsor mc, int on); /* no locality renumbering inside the colours (hierarchy levels) */
 /* pmg_parsor.c: data-flow form of PCPARSOR's multi-rank sweep; the four arrays are malloc'ed, the caller frees them */
@@ -105,6 +111,10 @@ pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains);
 pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *Y_lay, void *stream);
 pmg_status pmg_mcsor_residual_chains(pmg_mcsor mc, int32_t nchains, const double *b_lay, int bcs, const double *Y_lay, double *R_lay, void *stream);
 pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc); /* PMG_ERR_SUP for what the chains kernels do not carry */
+pmg_lrc    pmg_mcsor_lrc(pmg_mcsor mc); /* the operator's low-rank update, NULL if none (borrowed) */
+/* pmg_mcsor_sweeps_chains (noisy) on an operator with a low-rank update: directional sweep i of the call takes its noise term from
+   eta_dev + i * eta_stride (k x C, drawn) onto B_lay (ld x C, the caller's own: written and put back) and is followed by the repair */
+pmg_status pmg_mcsor_sweeps_lowrank_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *eta_dev, int64_t eta_stride, double *B_lay, double *Y_lay, void *stream);
 const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc);      /* layout -> natural row map on the device (-1 in pad rows) */
 /* pmg_chol.c: the exact sample y = L^-T (L^-1 b + xi) on C right-hand sides; Xi, V: n x C work arrays */
 pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *keys_dev, uint64_t counter, const double *B, double *Y, double *Xi, double *V, void *stream);

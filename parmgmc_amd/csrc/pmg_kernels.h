@@ -204,6 +204,17 @@ int pmgk_lrc_btx_chains_nblocks(int64_t n, int compact);
 int pmgk_lrc_btx_chains(int64_t n, const int64_t *rows, int k, const double *M, int64_t ldm, const double *Y, int32_t nchains, double *partial, const double *scale, double *out, void *stream);
 int pmgk_lrc_axpy_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, void *stream);
 int pmgk_lrc_noise_chains(int k, int32_t nchains, const uint64_t *keys, uint64_t tag, uint64_t sweep, const double *sqrtS, double *eta, void *stream);
+/* the chains V-cycle's forms: the update that keeps / puts back right-hand side entries, the one-workgroup form of a small support,
+   all noise terms of a cycle (entry i: level[i]'s row of the key table, draws ctr0[i] + d at the slots first[i] + d; first ascending) */
+int pmgk_lrc_axpy_save_chains(int64_t nr, const int64_t *rows, int k, const double *M, int64_t ldm, const double *coef, double sign, const double *in, int in_cs, double *out, int32_t nchains, double *save_out, const double *restore, double *rdst, void *stream);
+int pmgk_lrc_small_chains(int64_t ns, const int64_t *rows, int k, const double *Mc, const double *Y, int32_t nchains, const double *scale, const double *M2, double sign, double *out, const double *restore, double *rdst, void *stream);
+#define PMGK_LRC_NOISE_PLAN_MAX 64
+typedef struct {
+  int      n;
+  int      level[PMGK_LRC_NOISE_PLAN_MAX], first[PMGK_LRC_NOISE_PLAN_MAX];
+  uint64_t ctr0[PMGK_LRC_NOISE_PLAN_MAX];
+} pmgk_lrc_noise_plan;
+int pmgk_lrc_noise_batch_chains(int nslots, int k, int32_t nchains, const uint64_t *keys, uint64_t tag, const pmgk_lrc_noise_plan *plan, const double *sqrtS, double *eta, void *stream);
 
 /* running statistics of the chains (kernels_chainstats.hip): one pass over a step's n x C array Y (chain fastest) merges its C
    samples per row into the running (mean, M2) and forms the nqoi weighted column sums w_q . Y[:, c]; every sum in an order that

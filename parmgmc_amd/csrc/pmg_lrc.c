@@ -56,6 +56,10 @@ struct pmg_lrc_s {
   /* many chains (pmg_lrc_rhs_chains / pmg_lrc_post_chains): k x ch_cap k-vectors and the block sums of B^T Y, first use */
   int32_t ch_cap;
   double *ch_eta, *ch_wk, *ch_partial;
+  /* the chains V-cycle (pmg_lrc_rhs_inplace_chains): the right-hand side entries under the noise term, (ns or ld) x ch_saved_cap,
+     and the vector that carries it until the next repair puts them back */
+  int32_t ch_saved_cap;
+  double *ch_saved, *ch_bmod;
 };
 
 void pmg_lrc_destroy(pmg_lrc *p)
@@ -81,6 +85,7 @@ void pmg_lrc_destroy(pmg_lrc *p)
   pmg_dev_free(l->ch_eta);
   pmg_dev_free(l->ch_wk);
   pmg_dev_free(l->ch_partial);
+  pmg_dev_free(l->ch_saved);
   free(l);
   *p = NULL;
 }
@@ -543,4 +548,70 @@ pmg_status pmg_lrc_post_chains(pmg_lrc l, int32_t C, int dir, double *Y_lay, voi
     PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->Bb[d], l->ld, l->ch_wk, -1.0, Y_lay, 1, Y_lay, C, stream));
   }
   return PMG_SUCCESS;
+}
+
+/* ---- the same inside the V-cycle of the chains (pmg_mgmc_sample_chains), in fewer launches: the noise terms come drawn (one
+   launch per cycle, pmgk_lrc_noise_batch_chains), the right-hand side is the cycle's own and takes the noise term in place, and a
+   support of one block of rows runs B^T y, its reduction and the update in one workgroup per 64 chains.  Same sums, same bits. */
+
+/* one block of support rows: the one-workgroup form (the single chain's lrc_small without its switch) */
+static int lrc_small_chains(pmg_lrc l) { return l->ns > 0 && l->ns <= pmgk_lrc_rows_per_block(); }
+
+int pmg_lrc_chains_fused(pmg_lrc l) { return l && lrc_small_chains(l); }
+
+/* B_lay (ld x C, written) += B (sqrt(S) o eta_c) on the support rows (every row in the dense form), eta_dev k x C drawn by the
+   caller; the old entries are kept and go back with the next pmg_lrc_post_restore_chains, bit for bit */
+pmg_status pmg_lrc_rhs_inplace_chains(pmg_lrc l, int32_t C, const double *eta_dev, double *B_lay, void *stream)
+{
+  PMG_CALL(lrc_chains_workspace(l, C, stream));
+  if (C > l->ch_saved_cap) {
+    PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
+    pmg_dev_free(l->ch_saved);
+    l->ch_saved     = NULL;
+    l->ch_saved_cap = 0;
+    PMG_CALL(pmg_dev_alloc((void **)&l->ch_saved, sizeof(double) * (size_t)(l->ns ? l->ns : l->ld) * (size_t)C));
+    l->ch_saved_cap = C;
+  }
+  PMG_CALL(lrc_flush_restore(l, stream)); /* a single-chain call's, should one be pending */
+  l->ch_bmod = NULL; /* (a cycle that ended in an error: its right-hand sides are rewritten before they are read again) */
+  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, l->Bc, l->ns, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved, NULL, NULL, stream));
+  else PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, l->B, l->ld, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved, NULL, NULL, stream));
+  l->ch_bmod = B_lay;
+  return PMG_SUCCESS;
+}
+
+/* out -= M2 (scale o (B^T X)) on C chains; restore: the entries pmg_lrc_rhs_inplace_chains kept go back in the update's pass */
+static pmg_status lrc_btx_update_chains(pmg_lrc l, int32_t C, const double *X_lay, const double *scale, const double *M2c, const double *M2d, double *out_lay, int restore, void *stream)
+{
+  const double *sv = restore ? l->ch_saved : NULL;
+  double       *bm = restore ? l->ch_bmod : NULL;
+  if (lrc_small_chains(l)) PMG_KERNEL(pmgk_lrc_small_chains(l->ns, l->rows, l->k, l->Bc, X_lay, C, scale, M2c, -1.0, out_lay, sv, bm, stream));
+  else if (l->ns) {
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, X_lay, C, l->ch_partial, scale, l->ch_wk, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, M2c, l->ns, l->ch_wk, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
+  } else {
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, X_lay, C, l->ch_partial, scale, l->ch_wk, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, M2d, l->ld, l->ch_wk, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
+  }
+  return PMG_SUCCESS;
+}
+
+/* pmg_lrc_post_chains that also ends the noise term of pmg_lrc_rhs_inplace_chains */
+pmg_status pmg_lrc_post_restore_chains(pmg_lrc l, int32_t C, int dir, double *Y_lay, void *stream)
+{
+  const int d = dir == PMG_SOR_FORWARD_SWEEP ? 0 : 1;
+  PMG_CALL(lrc_chains_workspace(l, C, stream));
+  PMG_CALL(lrc_flush_restore(l, stream));
+  l->bty_vec = NULL;
+  PMG_CALL(lrc_btx_update_chains(l, C, Y_lay, NULL, l->Bbc[d], l->Bb[d], Y_lay, l->ch_bmod != NULL, stream));
+  l->ch_bmod = NULL;
+  return PMG_SUCCESS;
+}
+
+/* R -= B (S o (B^T X)) on C chains (pmg_lrc_residual_sub per column) */
+pmg_status pmg_lrc_residual_sub_chains(pmg_lrc l, int32_t C, const double *X_lay, double *R_lay, void *stream)
+{
+  PMG_CALL(lrc_chains_workspace(l, C, stream));
+  PMG_CALL(lrc_flush_restore(l, stream));
+  return lrc_btx_update_chains(l, C, X_lay, l->S, l->Bc, l->B, R_lay, 0, stream);
 }

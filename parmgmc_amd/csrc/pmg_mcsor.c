@@ -787,12 +787,14 @@ pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains)
   return PMG_SUCCESS;
 }
 
-/* what the V-cycle of the chains carries (pmg_mgmc_sample_chains); the MCSOR entry points take the low-rank update themselves */
+/* what the V-cycle of the chains carries (pmg_mgmc_sample_chains): a low-rank update on one device */
 pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc)
 {
-  PMG_CHECK(!mc->lrc, PMG_ERR_SUP, "multi-chain sampling of an operator with a low-rank (MATLRC) update is not supported");
+  PMG_CHECK(!mc->lrc || pmg_lrc_is_local(mc->lrc), PMG_ERR_SUP, "multi-chain sampling of an operator with a low-rank (MATLRC) update over several ranks is not supported");
   return PMG_SUCCESS;
 }
+
+pmg_lrc pmg_mcsor_lrc(pmg_mcsor mc) { return mc ? mc->lrc : NULL; }
 
 const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc) { return mc->S.orig; }
 
@@ -854,10 +856,32 @@ static pmg_status mcsor_sweeps_lrc_chains(pmg_mcsor mc, int32_t nchains, const u
   return PMG_SUCCESS;
 }
 
+/* the sweeps of the chains V-cycle on such an operator: per directional sweep the noise term in place (one launch), the colour
+   sweeps, the repair with the restore (one launch on a small support, else three) */
+pmg_status pmg_mcsor_sweeps_lowrank_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *eta_dev, int64_t eta_stride, double *B_lay, double *Y_lay, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  pmgk_sell S = mc->S;
+  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
+  uint64_t  ctr  = counter0;
+  const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+  for (int32_t i = 0; i < its * ndir; ++i) {
+    const int      dir   = ndir == 2 ? (i % 2 == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
+    const uint64_t sweep = ctr++;
+    PMG_CALL(pmg_lrc_rhs_inplace_chains(mc->lrc, nchains, eta_dev + (int64_t)i * eta_stride, B_lay, stream));
+    PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, 1, sweep, B_lay, 1, Y_lay, stream));
+    PMG_CALL(pmg_lrc_post_restore_chains(mc->lrc, nchains, dir, Y_lay, stream));
+  }
+  if (counter_out) *counter_out = ctr;
+  return PMG_SUCCESS;
+}
+
+/* R = b - A Y per chain, A the operator with its low-rank update (pmg_mcsor_residual_layout per column) */
 pmg_status pmg_mcsor_residual_chains(pmg_mcsor mc, int32_t nchains, const double *b_lay, int bcs, const double *Y_lay, double *R_lay, void *stream)
 {
   PMG_CALL(mcsor_ready(mc));
   PMG_KERNEL(pmgk_sell_residual_chains(&mc->S, nchains, b_lay, bcs, Y_lay, R_lay, stream));
+  if (mc->lrc) PMG_CALL(pmg_lrc_residual_sub_chains(mc->lrc, nchains, Y_lay, R_lay, stream));
   return PMG_SUCCESS;
 }
 

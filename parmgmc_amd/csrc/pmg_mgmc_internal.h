@@ -102,6 +102,8 @@ struct pmg_mgmc_s {
   pmg_keybuf ch_keys;            /* level_seed(seeds[c], l) at l * C + c */
   double    *ch_B;               /* one right-hand side per chain in the finest level's layout (pmg_mgmc_sample_chains_rhs), ld x ch_B_cap */
   int32_t    ch_B_cap;
+  double    *ch_eta;             /* the low-rank noise terms of one cycle: (directional sweeps of the levels with an update) x k x C */
+  int64_t    ch_eta_cap;         /* ... in doubles */
 };
 
 typedef struct {

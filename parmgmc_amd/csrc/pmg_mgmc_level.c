@@ -91,6 +91,20 @@ pmg_status pmg_mgmc_level_lowrank_factors(pmg_mgmc h, int32_t level, int32_t *k,
   return pmg_lrc_get_compact(l, k, ns, rows_host, B_host, Bb_fwd_host, Bb_bwd_host);
 }
 
+/* what the low-rank passes of a level run over, on every kind of level (a sliced-ELL level's sampler holds its update itself):
+   the rank, the number of rows (the support rows of the row-compact form, every row of the dense form: *dense = 1) */
+pmg_status pmg_mgmc_level_lowrank_sizes(pmg_mgmc h, int32_t level, int32_t *k, int64_t *rows, int *dense)
+{
+  mg_level *Lv;
+  PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
+  pmg_lrc l = mg_level_lrc(Lv);
+  if (!l && Lv->mc) l = pmg_mcsor_lrc(Lv->mc);
+  PMG_CHECK(l, PMG_ERR_ARG_WRONGSTATE, "level %d carries no low-rank update", level);
+  pmg_lrc_get_sizes(l, k, rows, dense);
+  if (dense && *dense && rows) *rows = (int64_t)level_rows(Lv);
+  return PMG_SUCCESS;
+}
+
 /* y -= Bb (B^T y) with the level's factors, MCSORPostSOR_LRC (src/mc_sor.c:101-112) */
 pmg_status pmg_mgmc_level_lowrank_post(pmg_mgmc h, int32_t level, int backward, double *y_lvl, void *stream)
 {

@@ -426,6 +426,12 @@ class MGMC:
         check(lib.pmg_mgmc_level_lowrank_factors(self._h, level, C.byref(k), C.byref(ns), rows.ctypes.data, B.ctypes.data, Bf.ctypes.data, Bb.ctypes.data))
         return rows, B, Bf, Bb
 
+    def level_lowrank_sizes(self, level: int):
+        """(k, rows, dense): rank of the level's update and the rows its passes run over, on every kind of level"""
+        k, rows, dense = C.c_int32(), C.c_int64(), C.c_int()
+        check(lib.pmg_mgmc_level_lowrank_sizes(self._h, level, C.byref(k), C.byref(rows), C.byref(dense)))
+        return k.value, rows.value, bool(dense.value)
+
     def level_lowrank_post(self, level: int, y, backward: bool = False):
         check(lib.pmg_mgmc_level_lowrank_post(self._h, level, int(backward), _ptr(y), _stream()))
 
@@ -466,7 +472,8 @@ class MGMC:
         for bit.  callback(it, Y) after every sample; a raised exception aborts the loop.  stats: a ChainStats(n, C) updated
         after every sample by the library's own callback instead (no Python in the loop; excludes callback).  cov: a
         ChainCov(n, C) that records the covariance error of every sample the same way; stats= and cov= together are updated by
-        one Python-level callback."""
+        one Python-level callback.  A hierarchy with set_lowrank samples the posterior A + B diag(S) B^T the same way (after
+        setup)."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()

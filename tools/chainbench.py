@@ -14,7 +14,9 @@ t = w @ Y; the merge on n-vectors); then MGMC chains with and without stats= (th
 --lowrank K: posterior lines instead, with K ball observations on the mesh vertices (column j = indicator of the vertices
 within --radius of centre j, divided by their count): the MATLRC sweep (mcgibbs, forward; pmg_mcsor_sample_chains on an
 operator with pmg_mcsor_set_lowrank) and Woodbury + MGMC chains (WoodburySampler.run_chains on the per-chain right-hand-side
-MGMC call), each beside its single-chain entry point (mcsor sample; the WoodburySampler.run loop).
+MGMC call), each beside its single-chain entry point (mcsor sample; the WoodburySampler.run loop); and MATLRC MGMC, the V-cycle on
+the hierarchy that carries the update on every level (MGMC.set_lowrank; mg.sample beside mg.sample_chains), one cycle per sample
+as the Woodbury line, with its ratio to that line.  --matlrc-only: only the MATLRC MGMC chains calls (for runs under rocprofv3).
 
 --cov: the covariance-error lines instead (pmg_chaincov_update; the config-4 mesh is not built): for n in {1024, 4096} x C in
 {32, 1000}, time per update (median of `regions` event-timed groups of 20 updates), n (n + 1) C flops over that time against the
@@ -62,6 +64,7 @@ def main():
     ap.add_argument("--sweep-only", action="store_true", help="only the chains sweep (for counter runs under rocprofv3)")
     ap.add_argument("--lowrank", type=int, default=0, help="K > 0: the posterior lines with K ball observations")
     ap.add_argument("--radius", type=float, default=0.1)
+    ap.add_argument("--matlrc-only", action="store_true", help="with --lowrank: only the MATLRC MGMC chains calls (for runs under rocprofv3)")
     ap.add_argument("--stats", action="store_true", help="the chain-statistics lines (pmg_chainstats_update)")
     ap.add_argument("--cov", action="store_true", help="the covariance-error lines (pmg_chaincov_update)")
     ap.add_argument("--cov-updates-only", action="store_true", help="with --cov: only the update groups (for runs under rocprofv3)")
@@ -95,7 +98,7 @@ def main():
     if args.stats:
         return stats_lines(args, n, mg, b)
     if args.lowrank:
-        return lowrank_lines(args, xy, A, mg, b)
+        return lowrank_lines(args, xy, A, mg, b, ops, ps)
     if args.sweep_only:
         for C in args.chains:
             Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
@@ -289,17 +292,30 @@ def ball_centres(xy, k):
     return fixed + [tuple(xy[i]) for i in rng.choice(len(xy), size=k - 3, replace=False)]
 
 
-def lowrank_lines(args, xy, A, mg, b):
+def lowrank_lines(args, xy, A, mg, b, ops, ps):
     import numpy as np
     import torch
 
-    from parmgmc_amd import COLORING_ITERATED, MCSOR
+    from parmgmc_amd import COLORING_ITERATED, MCSOR, MGMC
     from parmgmc_amd.unstructured import ball_observations
     from parmgmc_amd.wrappers import WoodburySampler
 
     n, its, k = A.shape[0], args.its, args.lowrank
     B = ball_observations(xy, ball_centres(xy, k), args.radius)
     S = np.linspace(40.0, 80.0, k)
+    # MGMC on the MATLRC hierarchy: the smoother and colouring of the prior hierarchy, the update on every level
+    mgl = MGMC.from_hierarchy(ops, ps)
+    mgl.set_coloring(COLORING_ITERATED)
+    mgl.set_smoother(True, 1.0, 1, 1)
+    mgl.set_lowrank(B, S)
+    mgl.setup()
+    if args.matlrc_only:
+        for C in args.chains:
+            seeds = [0xCAFE + 7919 * c for c in range(C)]
+            Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+            ms = timed(lambda: mgl.sample_chains(b, Y, its, seeds), args.regions)
+            print(json.dumps({"chains": C, "its": its, "lowrank": k, "matlrc_mgmc_ms_per_cycle": ms / its, "finite": bool(torch.isfinite(Y).all().item())}), flush=True)
+        return
     mc = MCSOR(A.indptr, A.indices, A.data, COLORING_ITERATED).setup()
     mc.set_lowrank(B, S)
     # the Woodbury set-up's solver: ten symmetric Gauss-Seidel sweeps of the prior operator (its quality does not change the timing)
@@ -318,8 +334,11 @@ def lowrank_lines(args, xy, A, mg, b):
     ms1_sw = timed(lambda: mc.sample(b, y, its, seed=0xCAFE), args.regions)
     y.zero_()
     ms1_wb = timed(lambda: wb.run(b, y, its, 0xCAFE), args.regions)
+    y.zero_()
+    ms1_ml = timed(lambda: mgl.sample(b, y, its, seed=0xCAFE), args.regions)
     single = {"lowrank_sweep_samples_per_s": its * 1e3 / ms1_sw, "lowrank_sweep_ms": ms1_sw / its,
-              "woodbury_mgmc_samples_per_s": its * 1e3 / ms1_wb, "woodbury_mgmc_ms": ms1_wb / its}
+              "woodbury_mgmc_samples_per_s": its * 1e3 / ms1_wb, "woodbury_mgmc_ms": ms1_wb / its,
+              "matlrc_mgmc_samples_per_s": its * 1e3 / ms1_ml, "matlrc_mgmc_ms": ms1_ml / its}
     print(json.dumps({"single_chain": single}), flush=True)
     for C in args.chains:
         seeds = [0xCAFE + 7919 * c for c in range(C)]
@@ -328,11 +347,16 @@ def lowrank_lines(args, xy, A, mg, b):
         ms_sw = timed(lambda: mc.sample_chains(b, Y, its, seeds), args.regions)
         Y.zero_()
         ms_wb = timed(lambda: wb.run_chains(b, Y, its, seeds), args.regions)
+        Y.zero_()
+        ms_ml = timed(lambda: mgl.sample_chains(b, Y, its, seeds), args.regions)
         rec = {"chains": C, "its": its, "lowrank": k,
                "lowrank_sweep": {"chain_samples_per_s": C * its * 1e3 / ms_sw, "ms_per_call": ms_sw, "ms_per_sweep": ms_sw / its,
                                  "vs_single": (C * its * 1e3 / ms_sw) / single["lowrank_sweep_samples_per_s"]},
                "woodbury_mgmc": {"chain_samples_per_s": C * its * 1e3 / ms_wb, "ms_per_call": ms_wb, "ms_per_sample": ms_wb / its,
                                  "vs_single": (C * its * 1e3 / ms_wb) / single["woodbury_mgmc_samples_per_s"]},
+               "matlrc_mgmc": {"chain_samples_per_s": C * its * 1e3 / ms_ml, "ms_per_call": ms_ml, "ms_per_cycle": ms_ml / its,
+                               "roofline": mgl.algorithmic_bytes_chains(C)[0] / (ms_ml / its * 1e-3) / HBM_PEAK,
+                               "vs_single": (C * its * 1e3 / ms_ml) / single["matlrc_mgmc_samples_per_s"], "time_over_woodbury_mgmc": ms_ml / ms_wb},
                "finite": bool(torch.isfinite(Y).all().item())}
         print(json.dumps(rec), flush=True)
         del Y
