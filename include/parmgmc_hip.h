@@ -399,7 +399,11 @@ pmg_status pmg_mgmc_set_level_interpolation_idx(pmg_mgmc mg, int32_t level, int6
 /* -mg_levels_pc_type sorgibbs (scaled = 0, omega = 1) | mcgibbs (scaled = 1, any omega, any sweep type);
    its = -mg_levels_ksp_max_it */
 pmg_status pmg_mgmc_set_smoother(pmg_mgmc mg, int scaled, double omega, int sweep_type, int32_t its);
-/* -mg_coarse_pc_type cholsampler (type 0) | Gibbs sweeps with -mg_coarse_ksp_max_it its (type 1) */
+/* -mg_coarse_pc_type cholsampler (type 0) | Gibbs sweeps with -mg_coarse_ksp_max_it its (type 1).  The coarse Gibbs
+   level has no parameters of its own: it is swept with the level smoother's (scaled, omega, sweep type) of
+   pmg_mgmc_set_smoother.  In the reference the coarse PC reads its own -mg_coarse_pc_mcgibbs_* keys; the PC layer
+   (pmg_pc_set_from_options on a gamgmc PC) therefore fails with PMG_ERR_SUP when the coarse sampler the options ask
+   for (sorgibbs: omega 1, forward; mcgibbs: its own omega and sweep keys) is not the one this rule gives. */
 pmg_status pmg_mgmc_set_coarse(pmg_mgmc mg, int type, int32_t its);
 /* literal != 0: every sample computes w = b - A y, work = MG(w), y += work exactly as src/pc_gamgmc.c:253-256 writes
    it.  Default (0): the same V-cycle run in place on (b, y) -- for stationary linear sweeps S(b, y) = y + S(b - A y, 0)

@@ -554,6 +554,7 @@ pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32
     if (cb) { /* pg->scb(it, y, ctx), src/pc_gamgmc.c:258 */
       PMG_CALL(lvl_from_layout(F, h->y_lay, y_nat, stream));
       const int rc = cb(it, y_nat, h->n_io, cbctx);
+      if (rc != 0 && counter_out) *counter_out = counter0 + (uint64_t)it + 1; /* y holds sample it: a resumed chain draws the next noise */
       PMG_CHECK(rc == 0, rc, "sample callback returned %d", rc);
     }
   }

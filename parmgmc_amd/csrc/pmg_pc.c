@@ -242,10 +242,11 @@ pmg_status pmg_pc_set_type(pmg_pc pc, const char *type)
     pc->data = NULL;
   }
   memset(&pc->ops, 0, sizeof pc->ops);
+  pc->type[0]     = 0; /* a failed lookup leaves an untyped PC, not the old name on no implementation */
+  pc->setupcalled = 0;
   for (int i = 0; i < pmg_ntypes; ++i)
     if (!strcmp(pmg_types[i].name, type)) {
       snprintf(pc->type, sizeof pc->type, "%s", type);
-      pc->setupcalled = 0;
       return pmg_types[i].ctor(pc);
     }
   PMG_FAIL(PMG_ERR_ARG_UNKNOWN_TYPE, "Unable to find requested PC type %s (call pmg_initialize first)", type);
@@ -525,6 +526,7 @@ static pmg_status PCCreate_MulticolorGibbs(pmg_pc pc) { return gibbs_ctor(pc, 1)
 pmg_status pmg_pc_mcgibbs_set_omega(pmg_pc pc, double omega)
 {
   PMG_CHECK(pc && !strcmp(pc->type, "mcgibbs"), PMG_ERR_ARG_WRONG, "not a mcgibbs PC");
+  PMG_CHECK(omega > 0.0 && omega < 2.0, PMG_ERR_ARG_OUTOFRANGE, "omega %g outside (0,2)", omega);
   ((pc_gibbs *)pc->data)->omega = omega;
   pc->setupcalled               = 0;
   return PMG_SUCCESS;
@@ -772,7 +774,7 @@ static pmg_status PCCreate_CholSampler(pmg_pc pc)
 /* ---------------------------------------------------------------------------------------------------- */
 typedef struct {
   pmg_mgmc mg;
-  int      levels, nu, coarse_its, smoother_mc, coarse_kind, sweep;
+  int      levels, nu, coarse_its, smoother_mc, coarse_kind, coarse_mc, sweep;
   double   omega;
 } pc_gamgmc;
 static pmg_status gamgmc_reset(pmg_pc pc) { return pmg_mgmc_destroy(&((pc_gamgmc *)pc->data)->mg); }
@@ -802,12 +804,43 @@ static pmg_status gamgmc_setfromoptions(pmg_pc pc) /* src/pc_gamgmc.c:299-366: d
   }
   if ((v = opt_find(pre, "-mg_coarse_pc_type"))) {
     if (!strcmp(v, "cholsampler")) d->coarse_kind = 0;
-    else if (!strcmp(v, "mcgibbs") || !strcmp(v, "sorgibbs")) d->coarse_kind = 1;
+    else if (!strcmp(v, "mcgibbs") || !strcmp(v, "sorgibbs")) d->coarse_kind = 1, d->coarse_mc = !strcmp(v, "mcgibbs");
     else PMG_FAIL(PMG_ERR_SUP, "coarse sampler %s", v);
   }
-  opt_real(pre, "-mg_levels_pc_mcgibbs_omega", &d->omega);
-  if (opt_bool(pre, "-mg_levels_pc_mcgibbs_symmetric")) d->sweep = PMG_SOR_SYMMETRIC_SWEEP;
-  if (opt_bool(pre, "-mg_levels_pc_mcgibbs_backward")) d->sweep = PMG_SOR_BACKWARD_SWEEP;
+  /* the level sampler is a real PC of its type: a mcgibbs one reads PetscOptionsRangeReal(omega, 0, 2), then forward,
+     backward, symmetric in this order, so the last one set wins (src/pc_mcgibbs.c:197-208); a sorgibbs one has none
+     of these keys */
+  if (d->smoother_mc) {
+    double om;
+    if (opt_real(pre, "-mg_levels_pc_mcgibbs_omega", &om)) {
+      PMG_CHECK(om > 0.0 && om < 2.0, PMG_ERR_ARG_OUTOFRANGE, "-%smg_levels_pc_mcgibbs_omega %g outside (0,2)", pre, om);
+      d->omega = om;
+    }
+    if (opt_bool(pre, "-mg_levels_pc_mcgibbs_forward")) d->sweep = PMG_SOR_FORWARD_SWEEP;
+    if (opt_bool(pre, "-mg_levels_pc_mcgibbs_backward")) d->sweep = PMG_SOR_BACKWARD_SWEEP;
+    if (opt_bool(pre, "-mg_levels_pc_mcgibbs_symmetric")) d->sweep = PMG_SOR_SYMMETRIC_SWEEP;
+  }
+  if (d->coarse_kind == 1) {
+    /* In the reference the coarse PC has its own options: sorgibbs is omega 1 forward, mcgibbs starts there and reads
+       its own keys.  The hierarchy sweeps its coarse Gibbs level with the level sampler's omega and sweep type
+       (pmg_mgmc_set_coarse), so a coarse sampler that differs from that cannot be run: an error, not another chain. */
+    const double have_om = d->smoother_mc ? d->omega : 1.0;
+    const int    have_sw = d->smoother_mc ? d->sweep : PMG_SOR_FORWARD_SWEEP;
+    double       want_om = 1.0;
+    int          want_sw = PMG_SOR_FORWARD_SWEEP;
+    const char  *key_om = "mg_coarse_pc_type", *key_sw = "mg_coarse_pc_type"; /* the key that asked for want_om, want_sw */
+    if (d->coarse_mc) {
+      if (opt_real(pre, "-mg_coarse_pc_mcgibbs_omega", &want_om)) {
+        key_om = "mg_coarse_pc_mcgibbs_omega";
+        PMG_CHECK(want_om > 0.0 && want_om < 2.0, PMG_ERR_ARG_OUTOFRANGE, "-%s%s %g outside (0,2)", pre, key_om, want_om);
+      }
+      if (opt_bool(pre, "-mg_coarse_pc_mcgibbs_forward")) want_sw = PMG_SOR_FORWARD_SWEEP, key_sw = "mg_coarse_pc_mcgibbs_forward";
+      if (opt_bool(pre, "-mg_coarse_pc_mcgibbs_backward")) want_sw = PMG_SOR_BACKWARD_SWEEP, key_sw = "mg_coarse_pc_mcgibbs_backward";
+      if (opt_bool(pre, "-mg_coarse_pc_mcgibbs_symmetric")) want_sw = PMG_SOR_SYMMETRIC_SWEEP, key_sw = "mg_coarse_pc_mcgibbs_symmetric";
+    }
+    PMG_CHECK(want_om == have_om, PMG_ERR_SUP, "-%s%s asks for a coarse Gibbs sampler with omega %g; the hierarchy sweeps its coarse level with the level sampler's omega %g", pre, key_om, want_om, have_om);
+    PMG_CHECK(want_sw == have_sw, PMG_ERR_SUP, "-%s%s asks for a coarse Gibbs sampler with sweep type %d; the hierarchy sweeps its coarse level with the level sampler's sweep type %d", pre, key_sw, want_sw, have_sw);
+  }
   pc->setupcalled = 0;
   return PMG_SUCCESS;
 }

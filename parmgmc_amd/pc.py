@@ -78,6 +78,9 @@ class PC:
     def set_type(self, t: str):
         check(lib.pmg_pc_set_type(self._h, t.encode()))
 
+    def set_options_prefix(self, prefix: str):
+        check(lib.pmg_pc_set_options_prefix(self._h, prefix.encode()))
+
     def get_type(self) -> str:
         buf = C.create_string_buffer(64)
         check(lib.pmg_pc_get_type(self._h, buf, 64))
@@ -136,6 +139,16 @@ class PC:
 
     def set_noise_counter(self, counter: int):
         check(lib.pmg_pc_set_noise_counter(self._h, counter))
+
+    # --- PCMulticolorGibbs / PCGAMGMC setters (reference include/parmgmc/pc/pc_mcgibbs.h:17-18, pc_gamgmc.h:15) ---
+    def mcgibbs_set_omega(self, omega: float):
+        check(lib.pmg_pc_mcgibbs_set_omega(self._h, omega))
+
+    def mcgibbs_set_sweep_type(self, t: int):
+        check(lib.pmg_pc_mcgibbs_set_sweep_type(self._h, t))
+
+    def gamgmc_set_levels(self, levels: int):
+        check(lib.pmg_pc_gamgmc_set_levels(self._h, levels))
 
     def woodbury_set_solver(self, solver: "PC"):
         """PCWoodburySetSolver (reference src/woodbury.c:185-198); the woodbury PC takes the inner PC over."""

@@ -5,6 +5,7 @@ import pytest
 import scipy.sparse as sp
 
 import oracle as O
+from mgmc_oracle import level_seed, oracle_chain, oracle_hierarchy  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 GOLD = 0x9E3779B97F4A7C15
@@ -19,25 +20,6 @@ def dev(a):
 
 def host(t):
     return t.detach().cpu().numpy()
-
-
-def level_seed(seed, l):
-    return (seed + GOLD * (l + 1)) & M64
-
-
-def oracle_hierarchy(nx, ny, nz, kappa, levels):
-    dims = [(nx, ny, nz)]
-    for _ in range(levels - 1):
-        dims.append(tuple((d - 1) // 2 + 1 if d > 1 else 1 for d in dims[-1]))
-    dims = dims[::-1]  # dims[0] coarsest
-    A = O.shifted_laplace(nx, ny, nz, kappa).scipy()
-    lv = [None] * levels
-    lv[levels - 1] = dict(A=A, P=None, dims=dims[-1])
-    for l in range(levels - 1, 0, -1):
-        P = O.q1_interp(*dims[l - 1])
-        lv[l]["P"] = P
-        lv[l - 1] = dict(A=O.galerkin(lv[l]["A"], P), P=None, dims=dims[l - 1])
-    return lv
 
 
 @pytest.mark.parametrize("grid,levels", [((9, 9, 1), 3), ((9, 5, 5), 2), ((17, 9, 9), 3)])
@@ -82,43 +64,6 @@ def test_chol_sampler_matches_oracle():
     with pytest.raises(PMGError) as e:
         CholSampler(bad.rowptr, bad.colidx, bad.vals)
     assert e.value.code == 81 and "leading minor of order 2" in str(e.value)
-
-
-def oracle_chain(grid, kappa, levels, b, y0, its, seed, counter0, guesszero, nu=1, scaled=False, omega=1.0, sweep=O.SOR_FORWARD, coarse="cholsampler", coarse_its=1, lv=None, shift=None):
-    """`lv`: a hierarchy from oracle_hierarchy(grid, kappa, levels) to reuse; `shift`: {level: k} moves that level's noise
-    counters by k draws (a negative control: the chain must then differ from the sampler's)"""
-    if lv is None:
-        lv = oracle_hierarchy(*grid, kappa, levels)
-    shift = shift or {}
-    top = levels - 1
-    csr = [O.CSR.from_scipy(x["A"]) for x in lv]
-    cols = [O.coloring_parity8(*x["dims"]) for x in lv]
-    cols[top] = O.coloring_redblack(*grid)
-    Lc = O.potrf_lower(csr[0].dense()) if coarse == "cholsampler" else None
-    y = np.array(y0, copy=True)
-    out = []
-    for it in range(its):
-        s = counter0 + it
-        ctr = {l: 64 * s + shift.get(l, 0) for l in range(levels)}
-
-        def noise(l):
-            c = ctr[l]
-            ctr[l] += 1
-            if l == top:
-                return O.noise_grid(*grid, level_seed(seed, l), c)
-            return O.noise_rows(csr[l].n, level_seed(seed, l), c)
-
-        def smooth(l, rhs, x, leg, its_=None):
-            return O.gibbs_samples(csr[l], cols[l], rhs, x, nu if its_ is None else its_, lambda d: noise(l), omega, sweep, scaled)
-
-        def coarse_fn(rhs):
-            if coarse == "cholsampler":
-                return O.chol_sample(Lc, rhs, noise(0))
-            return smooth(0, rhs, np.zeros(csr[0].n), 0, coarse_its)
-
-        y = O.gamgmc_richardson(lv, b, y, 1, guesszero and it == 0, smooth, coarse_fn)
-        out.append(y.copy())
-    return out
 
 
 @pytest.mark.parametrize("literal", [False, True], ids=["in_place", "correction_form"])

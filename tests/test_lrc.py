@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from mgmc_oracle import LrcMgmcOracle  # noqa: F401
 
 ETA_TAG = 0x632BE59BD9B4E019
 M64 = (1 << 64) - 1
@@ -148,59 +149,6 @@ def mg_hierarchy(grid, kappa, levels):
         lv[l]["P"] = O.q1_interp(*dims[l - 1])
         lv[l - 1] = dict(A=O.galerkin(lv[l]["A"], lv[l]["P"]), P=None, dims=dims[l - 1])
     return lv
-
-
-class LrcMgmcOracle:
-    """The oracle's restatement of PCGAMGMC on a MATLRC operator: the hierarchy of the base matrix, per-level
-    factors B_l, level samplers = LRC Gibbs sweeps (src/mc_sor.c:101-112, src/pc_mcgibbs.c:130-140), level residuals
-    with the LRC operator (src/pc_gamgmc.c:186-194), coarse = Cholesky of the explicit sum (src/pc_chols.c:119-153)."""
-
-    def __init__(self, lv, colors, B, S, nu=1, omega=1.0, sweep=O.SOR_FORWARD, scaled=True, coarse="cholsampler", coarse_its=1):
-        self.base, self.colors, self.S = lv, colors, np.asarray(S, float)
-        self.nu, self.omega, self.sweep, self.scaled, self.coarse, self.coarse_its = nu, omega, sweep, scaled, coarse, coarse_its
-        self.Bl = O.lrc_level_factors(lv, B)
-        self.csr = [O.CSR.from_scipy(x["A"]) for x in lv]
-        self.lv = [dict(A=O.LRCOperator(x["A"], self.Bl[l], self.S), P=x["P"]) for l, x in enumerate(lv)]
-        dirs = [O.SOR_FORWARD, O.SOR_BACKWARD]
-        self.Bb = [{d: O.lrc_build_correction(self.csr[l], colors[l], self.Bl[l], self.S, omega, d) for d in dirs} for l in range(len(lv))]
-        self.sd = [O.sqrtdiag(self.csr[l], omega, scaled) for l in range(len(lv))]
-        self.Lc = O.potrf_lower(self.lv[0]["A"].dense()) if coarse == "cholsampler" else None
-        self.ndir = 2 if sweep == O.SOR_SYMMETRIC else 1
-
-    def draws_per_smooth(self, l):
-        return (self.coarse_its if (l == 0 and self.coarse == "gibbs") else self.nu) * self.ndir
-
-    def sweeps(self, l, rhs, x, its, xi_fn, eta_fn):
-        """its samples of the level sampler; xi_fn(d) / eta_fn(d) = the d-th directional sweep's draws"""
-        d = 0
-        sq = np.sqrt(np.abs(self.S))
-        for _ in range(its):
-            for direction in ([O.SOR_FORWARD, O.SOR_BACKWARD] if self.sweep == O.SOR_SYMMETRIC else [self.sweep]):
-                w = O.prepare_rhs(xi_fn(d), self.sd[l], rhs) + self.Bl[l] @ (sq * eta_fn(d))
-                d += 1
-                x = O.lrc_mcsor_apply(self.csr[l], self.colors[l], self.Bl[l], self.Bb[l][O.SOR_FORWARD], self.Bb[l][O.SOR_BACKWARD], w, x, self.omega, direction)
-        return x
-
-    def chain(self, b, y, its, guesszero, xi, eta, chol_xi):
-        """xi(l, c) / eta(l, c): the c-th draw of level l in this chain call (c counts from 0 per SAMPLE via the
-        caller's closures); chol_xi(c) the coarse Cholesky draw."""
-        top = len(self.lv) - 1
-        for it in range(its):
-            ctr = {l: 0 for l in range(top + 1)}
-
-            def smooth(l, rhs, x, leg, n=None):
-                n = self.nu if n is None else n
-                c0 = ctr[l]
-                ctr[l] += n * self.ndir
-                return self.sweeps(l, rhs, x, n, lambda d: xi(it, l, c0 + d), lambda d: eta(it, l, c0 + d))
-
-            def coarse_fn(rhs):
-                if self.coarse == "cholsampler":
-                    return O.chol_sample(self.Lc, rhs, chol_xi(it))
-                return smooth(0, rhs, np.zeros(len(rhs)), 0, self.coarse_its)
-
-            y = O.gamgmc_richardson(self.lv, b, y, 1, guesszero and it == 0, smooth, coarse_fn)
-        return y
 
 
 @pytest.mark.parametrize("coarse", ["cholsampler", "gibbs"])
