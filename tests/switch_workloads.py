@@ -1,6 +1,7 @@
 """Child process of test_gpu_switches.py: runs one fixed set of workloads in a fresh process (the PMG_* runtime switches
 are read once per process, so every configuration needs a process of its own) and writes the raw float64 results to an
-.npz.  Keys starting with "meta/" are layout facts that show a switch took effect (line strides, AIJ row layouts); all
+.npz -- single-device grid sweeps, one chain through the in-kernel halo kernel (ipc loopback), V-cycles, AIJ samplers.
+Keys starting with "meta/" are layout facts that show a switch took effect (line strides, AIJ row layouts); all
 other keys are results that must not change by a bit.
 
     python switch_workloads.py <out.npz> <config4.npz>
@@ -12,10 +13,15 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent
 
-# GridMCSOR.sample: part-A shapes, a tail-mapped, banded + flat grid (255 = 4 x 64 threads per line, no tail: the plain
-# one-line-per-wavefront mapping) and TAIL_GRIDS of test_gpu_grid.py
+# GridMCSOR.sample: part-A shapes, a tail-mapped, banded + flat grid, the plain one-line-per-wavefront mapping (255 = 4 x 64
+# threads per line, no tail; 170 = 43 threads in one wavefront; 400 = 100 threads in two: flat over bands of 7 lines, banded
+# by whole line tiles, flat with two wavefronts per line -- SHAPE_BRANCHES of grid_mappings.py) and TAIL_GRIDS of test_gpu_grid.py
 GRID_SHAPES = [(257, 9, 9, 2.0), (287, 5, 5, 1.0), (255, 65, 3, 1.0), (65, 65, 5, 2.0),
-               (257, 5, 3, 10.0), (261, 3, 2, 1.0), (287, 2, 1, 0.5), (513, 2, 2, 2.0), (257, 70, 2, 1.0)]
+               (257, 5, 3, 10.0), (261, 3, 2, 1.0), (287, 2, 1, 0.5), (513, 2, 2, 2.0), (257, 70, 2, 1.0),
+               (170, 62, 3, 1.0), (170, 64, 3, 2.0), (400, 62, 3, 1.0)]
+# the in-kernel halo kernel in this process (IpcSlabDriver loopback: the rank is its own z-neighbour): HALO_TRACE_SHAPE of
+# grid_mappings.py, the plain mapping in XCD bands of 9 lines with a short last band
+HALO_SHAPE = (170, 66, 2, 1.5)
 GRID_SETTINGS = [(1.0, 1, True), (1.0, 2, False), (1.3, 3, True)]  # (omega, sweep type, scaled)
 
 # MGMC.sample: the part-A shapes of test_gpu_vcycle_shapes_oracle.py, and one of 8.5 M points where the fused residual +
@@ -55,6 +61,26 @@ def grid_runs(out):
             g.sample(_dev(b), y, 3, seed=0xBEEF, counter0=1, scaled=scaled)
             out[f"grid/{nx}x{ny}x{nz}/om{om}/t{t}"] = _host(y)
         g.destroy()
+
+
+def halo_run(out):
+    from parmgmc_amd import GridMCSOR
+    from parmgmc_amd.dist import IpcSlabDriver
+
+    nx, ny, nz, kappa = HALO_SHAPE
+    n = nx * ny * nz
+    rng = np.random.default_rng(n)
+    b0, y0 = rng.standard_normal(n), rng.standard_normal(n)
+    g = GridMCSOR(nx, ny, nz, kappa)
+    drv = IpcSlabDriver(g, 0, 1, loopback=True)
+    b = g.to_cvec(_dev(b0))
+    for om, t, scaled in GRID_SETTINGS:
+        g.set_omega(om)
+        y = g.to_cvec(_dev(y0))
+        drv.sample_cvec(b, y, 3, scaled, t, 0xBEEF, 1)
+        out[f"halo/{nx}x{ny}x{nz}/om{om}/t{t}"] = _host(g.from_cvec(y))
+    drv.destroy()
+    g.destroy()
 
 
 def mg_run(grid, levels, setting, its, guesszero=False):
@@ -127,6 +153,7 @@ def main(argv):
 
     out = {}
     grid_runs(out)
+    halo_run(out)
     mg_runs(out)
     aij_runs(out, argv[2])
     torch.cuda.synchronize()

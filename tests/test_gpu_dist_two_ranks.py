@@ -11,6 +11,8 @@ import socket
 import numpy as np
 import pytest
 
+from grid_mappings import HALO_RANK_SHAPES, HALO_SHAPES, HALO_VCYCLE_SHAPES
+
 pytestmark = pytest.mark.gpu
 
 
@@ -48,14 +50,22 @@ def _worker(rank, world, port, nx, ny, nz, kappa, omega, sweep_type, its, q, tra
     dist.destroy_process_group()
 
 
-@pytest.mark.parametrize("sweep_type,world,transport,nz", [(1, 2, None, 11), (3, 3, None, 11), (1, 2, "ipc", 11), (3, 3, "ipc", 11), (2, 4, "ipc", 11), (3, 5, "ipc", 6)], ids=["fwd-2-torch", "sym-3-torch", "fwd-2-ipc", "sym-3-ipc", "bwd-4-ipc", "sym-5-ipc-one-plane-slabs"])
-def test_ranks_on_one_gpu_reproduce_the_single_device_chain(sweep_type, world, transport, nz):
+# 40 x 18 packs its lines into wavefronts; the last three run the in-kernel halo kernel one line per wavefront (HALO_RANK_SHAPES
+# of grid_mappings.py): XCD bands of 9 lines with a short last band, bands of 8 with a last band of 5 on one-plane slabs, and three
+# wavefronts per line -- where the planes received from the neighbours are really used, unlike in the loopback test below
+RANK_CASES = [(1, 2, None, 11, 40, 18), (3, 3, None, 11, 40, 18), (1, 2, "ipc", 11, 40, 18), (3, 3, "ipc", 11, 40, 18), (2, 4, "ipc", 11, 40, 18), (3, 5, "ipc", 6, 40, 18),
+              (3, 3, "ipc", 7, 170, 66), (2, 5, "ipc", 6, 170, 61), (1, 2, "ipc", 4, 513, 66)]
+assert {(nx, ny, nz, world) for _, world, _, nz, nx, ny in RANK_CASES[6:]} == set(HALO_RANK_SHAPES)
+
+
+@pytest.mark.parametrize("sweep_type,world,transport,nz,nx,ny", RANK_CASES, ids=["fwd-2-torch", "sym-3-torch", "fwd-2-ipc", "sym-3-ipc", "bwd-4-ipc", "sym-5-ipc-one-plane-slabs", "sym-3-ipc-170x66-bands-of-9", "bwd-5-ipc-170x61-one-plane-slabs", "fwd-2-ipc-513x66-three-wavefronts"])
+def test_ranks_on_one_gpu_reproduce_the_single_device_chain(sweep_type, world, transport, nz, nx, ny):
     import torch
     import torch.multiprocessing as mp
 
     from parmgmc_amd import GridMCSOR
 
-    nx, ny, kappa, omega, its = 40, 18, 1.5, 1.1, 3  # nz = 6 on 5 ranks: slabs of 2, 1, 1, 1, 1 planes (one plane = both faces)
+    kappa, omega, its = 1.5, 1.1, 3  # nz = 6 on 5 ranks: slabs of 2, 1, 1, 1, 1 planes (one plane = both faces)
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _free_port()
@@ -107,6 +117,48 @@ def test_rccl_driver_loopback_on_one_gpu():
         for side in (0, 1):
             own, ghost, n = g.halo_plane(c, side)
             assert torch.equal(y[ghost:ghost + n], y[own:own + n]) and float(y[own:own + n].abs().sum()) > 0
+
+
+@pytest.mark.parametrize("shape", list(HALO_SHAPES), ids=["x".join(map(str, s)) for s in HALO_SHAPES])
+def test_ipc_driver_loopback_runs_the_halo_kernel_on_every_mapping(shape):
+    """The sample loop of the "ipc" transport on ONE GPU in one process: the rank is its own z-neighbour for the halo, so
+    grid_color_sweep_kernel<*, *, HALO> runs with its flag waits, peer stores and report count, on the mappings the halo rule
+    selects (HALO_SHAPES of grid_mappings.py: plain, XCD bands of whole line tiles, a short last band, bands of 9 lines with
+    sentinel lines, one plane that is both faces, three wavefronts per line, and packed as the control).  Both faces are
+    physical boundaries -- the received planes enter with coefficient 0 --, so every chain must equal the plain sampler's bit
+    for bit; the halo is periodic, so afterwards each ghost plane holds the opposite face's owned plane."""
+    import torch
+
+    from parmgmc_amd import GridMCSOR
+    from parmgmc_amd.dist import IpcSlabDriver
+
+    (nx, ny, nz), kappa = shape, 2.0
+    rng = np.random.default_rng(nx + ny + nz)
+    b0, y0 = rng.standard_normal(nx * ny * nz), rng.standard_normal(nx * ny * nz)
+    g, ref = GridMCSOR(nx, ny, nz, kappa), GridMCSOR(nx, ny, nz, kappa)
+    drv = IpcSlabDriver(g, 0, 1, loopback=True)
+    b = g.to_cvec(torch.as_tensor(b0, device="cuda"))
+    try:
+        for om, scaled in [(1.0, True), (1.2, True), (1.0, False)]:  # both OMEGA1 instantiations
+            g.set_omega(om)
+            ref.set_omega(om)
+            for t in (1, 2, 3):
+                y, yr = g.to_cvec(torch.as_tensor(y0, device="cuda")), ref.to_cvec(torch.as_tensor(y0, device="cuda"))
+                ctr = drv.sample_cvec(b, y, 2, scaled, t, 17, 5)
+                torch.cuda.synchronize()
+                drv.check()
+                ref.set_sweep_type(t)
+                assert ref.sample_cvec(b, yr, 2, 17, 5, scaled) == ctr == 5 + (4 if t == 3 else 2)
+                got, want = g.from_cvec(y).cpu().numpy(), ref.from_cvec(yr).cpu().numpy()
+                assert np.array_equal(got, want), (shape, om, scaled, t, np.abs(got - want).max())
+                assert not np.array_equal(got, y0)
+                for c in (0, 1):
+                    for side in (0, 1):
+                        _, ghost, n = g.halo_plane(c, side)
+                        own, _, _ = g.halo_plane(c, 1 - side)
+                        assert torch.equal(y[ghost:ghost + n], y[own:own + n]) and float(y[own:own + n].abs().sum()) > 0, (om, scaled, t, c, side)
+    finally:
+        drv.destroy()
 
 
 def _mg_worker(rank, world, port, grid, kappa, levels, opts, its, q, transport):
@@ -164,6 +216,8 @@ def _ball_factors(grid, k=3):
 
 
 MG_DEFAULT = dict(scaled=False, omega=1.0, sweep=1, nu=1, coarse="cholsampler", coarse_its=1, literal=False, env={})
+MG_UNPACKED_HALO = list(HALO_VCYCLE_SHAPES)  # grid levels that the slabs sweep one line per wavefront under the halo hand-shake
+assert MG_UNPACKED_HALO == [(513, 9, 9), (513, 65, 9)]
 
 
 @pytest.mark.parametrize("grid,levels,world,opts", [
@@ -177,7 +231,9 @@ MG_DEFAULT = dict(scaled=False, omega=1.0, sweep=1, nu=1, coarse="cholsampler", 
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400"}, "lowrank": True, "lowrank_k": 64, "scaled": True, "sweep": 3}),  # the top of the rank range
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_ST27_PAIR_SLAB": "0"}, "sweep": 2}),  # one launch per colour on the distributed class-stencil levels
     ((17, 17, 33), 4, 3, {"env": {"PMG_MG_REPLICATE_BELOW": "400", "PMG_GRID_FUSED_RR_SLAB": "0"}, "sweep": 3}),  # residual and restriction of the grid slabs as two kernels
-], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks", "lowrank_k64_3ranks", "st27_pair_slab_0_3ranks", "fused_rr_slab_0_3ranks"])
+    (MG_UNPACKED_HALO[0], 3, 2, {}),                                                            # grid level one line per wavefront under the halo hand-shake: three wavefronts per line (HALO_VCYCLE_SHAPES of grid_mappings.py)
+    (MG_UNPACKED_HALO[1], 3, 3, {"scaled": True, "sweep": 3}),                                 # the same in XCD bands of 9 lines with a last band of 2
+], ids=["replicated", "slab_levels_3ranks", "symmetric_gibbs_coarse_4ranks", "literal_backward", "one_plane_per_rank_5ranks", "lowrank_3ranks", "lowrank_literal_2ranks", "lowrank_k64_3ranks", "st27_pair_slab_0_3ranks", "fused_rr_slab_0_3ranks", "513x9x9_2ranks_unpacked_halo", "513x65x9_3ranks_banded_halo"])
 def test_distributed_vcycle_reproduces_the_single_device_chain(grid, levels, world, opts):
     """z-slab MGMC (pmg_mgmc_create_dmda_slab) with `world` ranks sharing the one GPU over the ipc transport: sweeps
     with per-phase halos, residual halo + restriction, all-gather into the replicated coarse part, prolongation onto

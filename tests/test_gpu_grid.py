@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 
 import oracle as O
+from grid_mappings import BAND_CONTROLS, BAND_SHAPES, SLAB_CUTS, SLAB_SHAPES, UNPACKED_SHAPES
 
 pytestmark = pytest.mark.gpu
 GOLD = Path(__file__).resolve().parent / "golden"
@@ -24,9 +25,13 @@ def host(t):
 GRIDS = [(9, 9, 1, 10.0), (5, 5, 5, 10.0), (6, 5, 4, 2.0), (2, 2, 2, 1.0), (3, 1, 1, 1.0), (33, 7, 3, 0.5), (64, 6, 5, 10.0), (70, 3, 2, 1.0), (128, 128, 1, 1e-4)]
 # lines of 64 m + a few threads (the multigrid sizes 2^k+1): full wavefronts + collected tail threads, kernels_grid.hip
 TAIL_GRIDS = [(257, 5, 3, 10.0), (261, 3, 2, 1.0), (287, 2, 1, 0.5), (513, 2, 2, 2.0), (257, 70, 2, 1.0)]
+# one line per wavefront: plain, XCD-banded by whole line tiles, flat with two wavefronts per line, tail + flat (which shape
+# reaches which: UNPACKED_SHAPES of grid_mappings.py, checked on the CPU by test_grid_mappings.py)
+UNPACKED_GRIDS = [s + (k,) for s, k in zip(UNPACKED_SHAPES, (10.0, 2.0, 1.0, 0.5))]
+assert [g[:3] for g in UNPACKED_GRIDS] == [(170, 6, 5), (170, 64, 3), (400, 62, 3), (513, 66, 2)]
 
 
-@pytest.mark.parametrize("grid", GRIDS + TAIL_GRIDS)
+@pytest.mark.parametrize("grid", GRIDS + TAIL_GRIDS + UNPACKED_GRIDS)
 @pytest.mark.parametrize("om", [1.0, 1.2])
 def test_deterministic_sweep_is_bit_exact(grid, om):
     """MCSORApply: fwd / bwd / sym on the HIP path == reference loop (src/mc_sor.c:256-289), bit for bit."""
@@ -93,7 +98,7 @@ def test_cvec_roundtrip_and_padding():
         assert np.count_nonzero(h) == x.size and np.isclose(np.sort(h[h != 0]), np.sort(x)).all()
 
 
-@pytest.mark.parametrize("grid", [(9, 9, 1, 10.0), (6, 5, 4, 2.0), (33, 7, 3, 0.5), (70, 3, 2, 1.0), (128, 128, 1, 10.0)] + TAIL_GRIDS[:4])  # (128, 128, 1) is BASELINE config 0 (ex1.c at 128x128)
+@pytest.mark.parametrize("grid", [(9, 9, 1, 10.0), (6, 5, 4, 2.0), (33, 7, 3, 0.5), (70, 3, 2, 1.0), (128, 128, 1, 10.0)] + TAIL_GRIDS[:4] + UNPACKED_GRIDS)  # (128, 128, 1) is BASELINE config 0 (ex1.c at 128x128)
 def test_noisy_chain_matches_oracle(grid):
     """PCApplyRichardson_MulticolorGibbs / _SORGibbs sample loop with in-kernel Philox + Box-Muller noise vs
     the oracle (libm log/cos/sin): tolerance 1e-13 relative to max|y| (device log/sincospi differ from glibc in
@@ -217,11 +222,67 @@ def test_slab_decomposition_is_bitwise_identical():
         assert np.array_equal(got, host(yd)), cuts
 
 
-def test_plane_range_sweeps_compose_to_the_full_sweep():
-    """boundary planes first, interior afterwards (the multi-GPU overlap order) == one full colour pass, bitwise."""
+SLAB_IDS = ["x".join(map(str, s)) for s in SLAB_SHAPES]
+
+
+@pytest.mark.parametrize("shape", list(SLAB_SHAPES), ids=SLAB_IDS)
+def test_slabs_on_the_unpacked_mappings_are_bitwise_identical(shape):
+    """The same decomposition where the slabs' sweeps run one line per wavefront (what the torch transport launches): the
+    compact tail mapping, whose line parity depends on kz0, tail threads, XCD bands and the flat walk on slabs that start at
+    odd and at even planes and on a one-plane slab -- forward sweeps and symmetric ones at omega = 1.1, bit for bit against
+    the single-domain chain."""
+    from parmgmc_amd import GridMCSOR
+    from parmgmc_amd.slab import SlabSet
+
+    (nx, ny, nz), kappa = shape, 3.0
+    rng = np.random.default_rng(nx + ny)
+    b, y0 = rng.standard_normal(nx * ny * nz), rng.standard_normal(nx * ny * nz)
+    for om, t in [(1.0, O.SOR_FORWARD), (1.1, O.SOR_SYMMETRIC)]:
+        one = GridMCSOR(nx, ny, nz, kappa)
+        one.set_omega(om)
+        one.set_sweep_type(t)
+        yd = dev(y0)
+        one.sample(dev(b), yd, 2, seed=99, counter0=3)
+        assert not np.array_equal(host(yd), y0)
+        for cuts in SLAB_CUTS:
+            ss = SlabSet(nx, ny, nz, kappa, cuts)
+            ss.set_omega(om)
+            ss.set_sweep_type(t)
+            got = ss.sample_natural(b, y0, 2, seed=99, counter0=3)
+            assert np.array_equal(got, host(yd)), (cuts, om, t)
+
+
+@pytest.mark.parametrize("shape", list(SLAB_SHAPES), ids=SLAB_IDS)
+def test_plane_ranges_of_a_slab_with_odd_kz0_compose_to_its_full_sweep(shape):
+    """the schedule of run_samples (first plane, last plane, interior) on the slab of planes 1..3 of six, its ghost planes
+    filled from the neighbouring slabs == one launch over the slab, bit for bit"""
+    from parmgmc_amd.slab import SlabSet
+
+    (nx, ny, nz), kappa, cuts = shape, 3.0, SLAB_CUTS[0]
+    assert cuts[1] & 1 and cuts[2] - cuts[1] >= 3
+    rng = np.random.default_rng(nx * ny)
+    plane = nx * ny
+    b, y0 = rng.standard_normal(plane * nz), rng.standard_normal(plane * nz)
+    ss = SlabSet(nx, ny, nz, kappa, cuts)
+    ss.set_omega(1.1)
+    bs = [s.to_cvec(dev(b[lo * plane:hi * plane])) for s, lo, hi in zip(ss.slabs, cuts, cuts[1:])]
+    ys = [s.to_cvec(dev(y0[lo * plane:hi * plane])) for s, lo, hi in zip(ss.slabs, cuts, cuts[1:])]
+    for c in (0, 1):
+        ss.exchange(ys, c)
+    g, bc, y1, y2 = ss.slabs[1], bs[1], ys[1].clone(), ys[1].clone()
+    assert g.kz0 == cuts[1] and g.nz == cuts[2] - cuts[1]
+    for c in (0, 1):
+        g.sweep_color_cvec(c, bc, y1, True, True, 5, 3)
+        for k0, nk in ((0, 1), (g.nz - 1, 1), (1, g.nz - 2)):
+            g.sweep_color_planes_cvec(c, k0, nk, bc, y2, True, True, 5, 3)
+    assert np.array_equal(host(y1), host(y2))
+    assert not np.array_equal(host(y1), host(ys[1]))
+
+
+def _plane_range_composition(grid):
     from parmgmc_amd import GridMCSOR
 
-    nx, ny, nz, kappa = 20, 18, 9, 1.5
+    nx, ny, nz, kappa = grid
     rng = np.random.default_rng(21)
     b, y0 = rng.standard_normal(nx * ny * nz), rng.standard_normal(nx * ny * nz)
     g = GridMCSOR(nx, ny, nz, kappa)
@@ -233,6 +294,12 @@ def test_plane_range_sweeps_compose_to_the_full_sweep():
         for k0, nk in ((0, 1), (nz - 1, 1), (1, nz - 2)):
             g.sweep_color_planes_cvec(c, k0, nk, bc, y2, True, True, 5, 3)
     assert np.array_equal(host(y1), host(y2))
+    return g, bc, y2
+
+
+def test_plane_range_sweeps_compose_to_the_full_sweep():
+    """boundary planes first, interior afterwards (the multi-GPU overlap order) == one full colour pass, bitwise."""
+    g, bc, y2 = _plane_range_composition((20, 18, 9, 1.5))
     from parmgmc_amd import PMGError
 
     with pytest.raises(PMGError) as e:
@@ -240,15 +307,31 @@ def test_plane_range_sweeps_compose_to_the_full_sweep():
     assert e.value.code == 63
 
 
-@pytest.mark.parametrize("ny", list(range(61, 73)) + [129, 257])
-def test_xcd_bands_of_any_remainder_sweep_every_line_once(ny):
-    """round 4: with >= 61 lines the single-device sweep deals the lines to eight XCD bands of floor(ny/8) (+1 for the last
-    ny mod 8 bands) and lets the wavefronts of a band walk its (plane, line) pairs without gaps (kernels_grid.hip, `zmain`).
-    Every remainder 0..7, an x tail (nx = 2^k+1 at ny = 129) and a plane range: deterministic sweeps bit for bit against the
-    reference loop, the noisy chain against the oracle, and boundary planes + interior == the full pass."""
+@pytest.mark.parametrize("grid", UNPACKED_GRIDS, ids=lambda g: "x".join(map(str, g[:3])))
+def test_plane_range_sweeps_compose_on_the_unpacked_mappings(grid):
+    """the same on the one-line-per-wavefront mappings: plain, XCD-banded, the flat walk (whose z layers are counted over
+    the planes of the range) and tail threads collected behind the range's last plane"""
+    _plane_range_composition(grid)
+
+
+BAND_CASES = sorted(BAND_SHAPES, key=lambda s: s[1]) + sorted(BAND_CONTROLS, key=lambda s: s[1])
+BAND_IDS = [str(s[1]) if s in BAND_SHAPES else f"packed-{s[0]}x{s[1]}" for s in BAND_CASES]
+
+
+@pytest.mark.parametrize("shape", BAND_CASES, ids=BAND_IDS)
+def test_xcd_bands_of_any_remainder_sweep_every_line_once(shape):
+    """round 4: with >= 61 lines and one line per wavefront the single-device sweep deals the lines to eight XCD bands of
+    floor(ny/8) (+1 for the last ny mod 8 bands) and lets the wavefronts of a band walk its (plane, line) pairs without gaps
+    (kernels_grid.hip, `zmain`).  nx = 170 (43 threads per line: not packed) at ny = 61..73 and 257: every remainder 0..7,
+    bands of 7 lines with five to seven of them one line longer (61..63), ny = 64 (whole line tiles: banded, no flat walk);
+    an x tail on top (nx = 2^k+1 at ny = 129); and a plane range.  The same line counts at nx = 12 pack their lines into
+    wavefronts and reach none of this: they stay as the packed controls (BAND_SHAPES / BAND_CONTROLS of grid_mappings.py
+    state which shape reaches which branch; test_grid_mappings.py holds them to it on the CPU).  Deterministic sweeps bit
+    for bit against the reference loop, the noisy chain against the oracle, and boundary planes + interior == the full
+    pass."""
     from parmgmc_amd import GridMCSOR
 
-    nx, nz, kappa = (257 if ny == 129 else 12), 5, 2.0
+    (nx, ny, nz), kappa = shape, 2.0
     A = O.shifted_laplace(nx, ny, nz, kappa)
     col = O.coloring_redblack(nx, ny, nz)
     rng = np.random.default_rng(ny)
@@ -276,7 +359,7 @@ def test_xcd_bands_of_any_remainder_sweep_every_line_once(ny):
     assert np.array_equal(host(y1), host(y2))
 
 
-@pytest.mark.parametrize("grid", [(6, 5, 4, 2.0), (70, 3, 2, 1.0), (64, 6, 5, 10.0)] + TAIL_GRIDS)
+@pytest.mark.parametrize("grid", [(6, 5, 4, 2.0), (70, 3, 2, 1.0), (64, 6, 5, 10.0)] + TAIL_GRIDS + UNPACKED_GRIDS)
 def test_residual_of_both_colours_matches_csr_product(grid):
     """r = b - A y (PCMG's residual, src/pc_gamgmc.c:253-254) from the one-launch kernel that handles both colours:
     row sums in CSR storage order, so bit-identical to the sequential CSR product."""

@@ -5,8 +5,9 @@ every result must be the default child's, byte for byte.
 A byte-equal A/B test also passes when a switch does nothing (a renamed variable, a shape that never reaches the
 branch).  So each configuration names the difference it must make: with rocprofv3 on PATH the children run under its
 kernel trace and the launches must differ from the default child's as stated in CONFIGS; layout switches show
-themselves in the child's own "meta/" facts.  SHAPE_BRANCHES records which thread mapping each part-A shape
-(test_gpu_vcycle_shapes_oracle.py) reaches on its grid level, checked against the default child's trace.
+themselves in the child's own "meta/" facts.  SHAPE_BRANCHES (grid_mappings.py) records which thread mapping each part-A
+shape (test_gpu_vcycle_shapes_oracle.py) and each GridMCSOR-only shape of the child reaches on its grid level, checked
+against the default child's trace, as is the launch of the in-kernel halo kernel on the plain unpacked mapping.
 
 The children run one after another, each with a time limit; the first one that fails stops the fixture."""
 import csv
@@ -20,6 +21,8 @@ from pathlib import Path
 import numpy as np
 import pytest
 
+from grid_mappings import HALO_TRACE_GSIZE, HALO_TRACE_SHAPE, SHAPE_BRANCHES, sweep_mapping
+
 pytestmark = pytest.mark.gpu
 HERE = Path(__file__).resolve().parent
 CHILD = HERE / "switch_workloads.py"
@@ -28,6 +31,7 @@ CHILD_TIMEOUT = 420  # s; a child takes well under a minute (torch start-up, set
 SWEEP_TAIL = r"grid_color_sweep_kernel<\w+, \w+, false, false, true>"
 SWEEP_PACKED = r"grid_color_sweep_kernel<\w+, \w+, false, true, false>"
 SWEEP_PLAIN = r"grid_color_sweep_kernel<\w+, \w+, false, false, false>"
+SWEEP_HALO_PLAIN = r"grid_color_sweep_kernel<\w+, \w+, true, false, false>"
 
 # configuration -> (environment, [(kind, pattern)]).  Kinds, each against the default child:
 #   gone: a kernel matching the pattern ran in the default child and not here;  new: the reverse;
@@ -59,52 +63,6 @@ CONFIGS = {
     "sell_locality_2": ({"PMG_SELL_LOCALITY": "2"}, [("meta", "meta/layout/lap99x99")]),
     "mg_fused_zero_0": ({"PMG_MG_FUSED_ZERO": "0"}, [("launches", r"fill_zero_kernel")]),
 }
-
-# part-A shape (grid level) -> the thread mapping of its grid sweep: tail threads collected in blocks of their own
-# (threads per line tplE >= 64, tplE % 64 <= 8), lines packed into wavefronts, XCD-banded dispatch (>= 16 line tiles),
-# flat (plane, line) runs over the bands (bands that are not whole line tiles).  Checked against the default child.
-SHAPE_BRANCHES = {
-    (257, 9, 9): dict(tail=True, packed=False, banded=False, flat=False),     # tplE 65: 1 tail thread per line
-    (287, 5, 5): dict(tail=True, packed=False, banded=False, flat=False),     # tplE 72: 8 tail threads
-    (257, 65, 9): dict(tail=True, packed=False, banded=True, flat=True),      # 17 line tiles, bands of 9 lines
-    (65, 65, 65): dict(tail=False, packed=True, banded=False, flat=False),
-    (129, 65, 17): dict(tail=False, packed=True, banded=False, flat=False),
-    (257, 257, 1): dict(tail=True, packed=False, banded=True, flat=True),     # bands of 33 lines
-    (9, 9, 129): dict(tail=False, packed=True, banded=False, flat=False),
-    (33, 3, 33): dict(tail=False, packed=True, banded=False, flat=False),
-    (5, 5, 5): dict(tail=False, packed=True, banded=False, flat=False),
-    (255, 65, 3): dict(tail=False, packed=False, banded=True, flat=True),     # GridMCSOR only: the plain unpacked mapping
-}
-
-
-def sweep_mapping(nx, ny, nz, tail_on=True, flat_on=True):
-    """The host's choice for a single-device grid sweep (grid_choose_mapping in kernels_grid.hip, default switches, the
-    tightest line stride of grids that fit the Infinity Cache): flags and the launch's grid size in work-items."""
-    half = (nx + 1) // 2
-    sx = (half + 1) // 2 * 2
-    tpl, tplE, nby = sx // 2, (half + 1) // 2, (ny + 3) // 4
-    tmain = tplE // 64 * 64
-    tailw = tplE - tmain
-    tail = tail_on and tmain > 0 and 0 < tailw <= 8
-    packed = not tail and 2 * ((tpl + 63) // 64 * 64) >= 3 * tplE
-    nbx = tplE if packed else (tmain // 64 if tail else (tpl + 63) // 64)
-    bandw = (ny + 7) // 8 if (not packed and nby >= 16) else 0
-    flat = False
-    if packed:
-        grid = ((ny * tplE + 255) // 256, 1, nz)
-    else:
-        gx, gy = (8 * nbx, (bandw + 3) // 4) if bandw else (nbx, nby)
-        zl = nz
-        if flat_on and bandw and ((bandw & 3) or 8 * bandw != ny):
-            flat = True
-            bw = ny // 8
-            maxband = bw + (1 if ny > 8 * bw else 0)
-            zl = (maxband * nz + 4 * gy - 1) // (4 * gy)
-        ztail = (nz * ((ny * tailw + 255) // 256) + gx * gy - 1) // (gx * gy) if tail else 0
-        grid = (gx, gy, zl + ztail)
-    flags = dict(tail=tail, packed=packed, banded=bandw > 0, flat=flat)
-    return flags, (grid[0] * 64, grid[1] * 4, grid[2])
-
 
 def _config4_npz(path):
     from parmgmc_amd.unstructured import assemble_p1, build_hierarchy, read_gmsh41_triangles, refine_uniform
@@ -227,10 +185,22 @@ def test_switch_reaches_its_kernels(runs, name):
 @pytest.mark.parametrize("shape", list(SHAPE_BRANCHES), ids=lambda s: "x".join(map(str, s)))
 def test_shape_reaches_its_grid_mapping(runs, shape):
     """the restatement of the host's mapping gives the table's branch, and the default child launched exactly that sweep"""
-    flags, gsize = sweep_mapping(*shape)
+    m = sweep_mapping(*shape)
+    flags, gsize = m.flags, m.gsize
     assert flags == SHAPE_BRANCHES[shape]
     (_, _, launches), _ = _get(runs, "default")
     if launches is None:
         pytest.skip("rocprofv3 not on PATH")
     pat = SWEEP_TAIL if flags["tail"] else (SWEEP_PACKED if flags["packed"] else SWEEP_PLAIN)
     assert any(g == gsize for _, g in _matching(launches, pat)), f"no {pat} launch of grid {gsize}"
+
+
+def test_halo_kernel_runs_on_the_plain_unpacked_mapping(runs):
+    """the loopback workload of the child launched the in-kernel halo kernel one line per wavefront (not packed, no tail), with
+    the grid the halo rule gives: XCD bands of ceil(ny / 8) lines, sentinel lines behind a short last band"""
+    m = sweep_mapping(*HALO_TRACE_SHAPE, halo=True)
+    assert not m.packed and not m.tail and m.banded and m.gsize == HALO_TRACE_GSIZE
+    (_, _, launches), _ = _get(runs, "default")
+    if launches is None:
+        pytest.skip("rocprofv3 not on PATH")
+    assert any(g == m.gsize for _, g in _matching(launches, SWEEP_HALO_PLAIN)), f"no {SWEEP_HALO_PLAIN} launch of grid {m.gsize}"

@@ -1,6 +1,6 @@
 """The whole geometric (DMDA) V-cycle against the oracle at the shapes where the host's kernel choices change: tail /
 packed / banded + flat thread mappings of the grid level (which shape reaches which: SHAPE_BRANCHES of
-test_gpu_switches.py, checked there against the kernel trace), class-stencil planes at the plane-kernel limit, wide
+grid_mappings.py, checked against the kernel trace in test_gpu_switches.py), class-stencil planes at the plane-kernel limit, wide
 class-stencil lines with a packed x remainder, 2-D and semicoarsened levels (no fused residual + restriction, general
 Q1 transfers), even extents on the coarsest levels and minimal extents -- under the settings that select the
 one-colour prolongation (omega = 1: forward, backward and symmetric skip different colours) and those that do not.
@@ -30,6 +30,8 @@ SHAPES = [
     ((9, 9, 129), 4),      # x / y reach extent 2 (even) on the coarsest levels while z keeps coarsening
     ((33, 3, 33), 2),      # minimal y extent
     ((5, 5, 5), 2),        # minimal grid
+    ((513, 9, 9), 3),      # tail mapping behind two full wavefronts per line; the single-device side of the distributed V-cycle
+                           # whose slabs sweep it one line per wavefront under the halo hand-shake (test_gpu_dist_two_ranks.py)
 ]
 IDS = ["x".join(map(str, g)) + f"-L{l}" for g, l in SHAPES]
 
