@@ -679,6 +679,31 @@ pmg_status pmg_chainstats_get_trace(pmg_chainstats cs, int32_t q, int32_t first,
 pmg_status pmg_gelman_rubin(int32_t chains, int64_t n, const double *vals_host, double *gr);
 /* the same on steps [first, first + count) of the trace of QOI q */
 pmg_status pmg_chainstats_rhat(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, double *gr);
+/* IACT (src/iact.c:73-92; examples/ex2.c:107) of every series of a device array at once: X_dev is n x nseries doubles, series
+   fastest, X[t * ld + s] with ld >= nseries (a window of the trace above is this layout with ld = nchains).  Per series, with
+   m = mean(x) and z_t = x_t - m:
+       c_k = sum_{t < n - k} z_t z_{t+k};   rho_k = c_k / c_0;   T_k = 2 (rho_0 + ... + rho_k) - 1   (running sum in lag order)
+       window = first k with k >= 5 T_k;   tau = T_window;   valid = (500 tau <= n)
+   -- pmg_iact's definitions with the autocorrelation formed directly instead of through an FFT, lag block by lag block
+   (PMG_IACT_LAG_BLOCK lags at a time) and only up to the block that holds the window: n (window + PMG_IACT_LAG_BLOCK)
+   multiply-adds per series.  A series with c_0 == 0 or a non-finite c_0 gives what pmg_iact gives: tau = NaN, window = n - 1,
+   valid = 0.  max_lag = 0: no limit, the reference's rule -- a chain that has not mixed then costs up to n^2 / 2 multiply-adds.
+   max_lag > 0: a series without a window at or below max_lag reports window = -1, tau = T_max_lag, valid = 0.
+   tau_host, window_host, valid_host: nseries host entries each (the last two may be NULL).  acf_dev: NULL, or nacf x nseries
+   device doubles that receive acf[k * nseries + s] = rho_k of series s for k < nacf (the scan then goes on to lag nacf - 1;
+   tau and window do not change); with acf_dev == NULL nacf is ignored.  The order of every sum is a function of (n, k) alone
+   (stated in kernels_iact.hip and DESIGN 11.4): no floating-point atomics, the same bits on every run and every stream,
+   whatever max_lag, nacf and the other series are.  The launches go to `stream`; the call SYNCHRONISES that stream to return
+   the host results.  The scratch (n x nseries doubles and the per-series results) lives for the call only.
+   All argument checks run before any device work.  PMG_ERR_ARG_NULL: X_dev or tau_host.  PMG_ERR_ARG_OUTOFRANGE: n < 2
+   ("Too few data points", src/iact.c:79), n >= 2^31, nseries < 1, ld < nseries, max_lag < 0, nacf outside [0, n]. */
+#define PMG_IACT_LAG_BLOCK 256
+pmg_status pmg_iact_chains(int64_t n, int32_t nseries, const double *X_dev, int64_t ld, int32_t max_lag, double *tau_host, int32_t *window_host, int32_t *valid_host, int32_t nacf, double *acf_dev, void *stream);
+/* the same on steps [first, first + count) of the trace of QOI q, read where it lies (no copy of the trace; nseries = nchains).
+   Synchronises the device before the launches (updates may have been enqueued on any stream) and `stream` after them.
+   PMG_ERR_ARG_NULL: the handle or tau_host.  PMG_ERR_ARG_OUTOFRANGE: q or the window outside what has been recorded,
+   count < 2 ("Too few data points"), max_lag < 0, nacf outside [0, count]. */
+pmg_status pmg_chainstats_iact(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, int32_t max_lag, double *tau_host, int32_t *window_host, int32_t *valid_host, int32_t nacf, double *acf_dev, void *stream);
 
 /* ---- covariance error over the chains on the device: the study of examples/ex6.c --------------------------------- */
 /* The ex6 consumer of pmg_*_sample_chains: EstimateCovarianceMatErrors (src/stats.c:94-117; examples/ex6.c:193) for chains

@@ -287,6 +287,8 @@ _sig = {
     "pmg_chainstats_get_trace": (_int, [_vp, _i32, _i32, _i32, _vp]),
     "pmg_gelman_rubin": (_int, [_i32, _i64, _vp, C.POINTER(_dbl)]),
     "pmg_chainstats_rhat": (_int, [_vp, _i32, _i32, _i32, C.POINTER(_dbl)]),
+    "pmg_iact_chains": (_int, [_i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pmg_chainstats_iact": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pmg_chaincov_create_chol": (_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "pmg_chaincov_create_dense": (_int, [_i32, _vp, _i32, _i32, C.POINTER(_vp)]),
     "pmg_chaincov_destroy": (_int, [C.POINTER(_vp)]),

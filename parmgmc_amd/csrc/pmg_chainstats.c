@@ -162,6 +162,16 @@ static pmg_status cs_window(pmg_chainstats h, int32_t q, int32_t first, int32_t 
   return PMG_SUCCESS;
 }
 
+/* the recorded steps [first, first + count) of QOI q where they lie: count x nchains device doubles, chain fastest (borrowed;
+   NULL while nothing has been recorded).  For pmg_chainstats_iact (pmg_iact.c). */
+pmg_status pmg_chainstats_trace_window(pmg_chainstats h, int32_t q, int32_t first, int32_t count, const double **X_dev, int32_t *nchains)
+{
+  PMG_CALL(cs_window(h, q, first, count));
+  *X_dev   = h->trace ? h->trace + ((int64_t)q * h->max_steps + first) * h->C : NULL;
+  *nchains = h->C;
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_chainstats_get_trace(pmg_chainstats h, int32_t q, int32_t first, int32_t count, double *vals_host)
 {
   PMG_CALL(cs_window(h, q, first, count));

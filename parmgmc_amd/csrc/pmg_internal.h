@@ -122,6 +122,9 @@ pmg_status pmg_chol_sample_chains(pmg_chol ch, int32_t nchains, const uint64_t *
 int32_t       pmg_chol_size(pmg_chol ch);
 const double *pmg_chol_inverse_factor_upper(pmg_chol ch);
 
+/* pmg_chainstats.c: steps [first, first + count) of QOI q of the trace on the device, count x nchains, chain fastest (borrowed) */
+pmg_status pmg_chainstats_trace_window(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, const double **X_dev, int32_t *nchains);
+
 /* pmg_rowblock.c */
 void pmg_mcsor_adopt_arrays(pmg_mcsor mc, int32_t *rowptr, int32_t *colidx, double *vals);
 

@@ -236,6 +236,15 @@ int pmgk_chaincov_syrk_matrix(int32_t n, int32_t K, const double *Y, const doubl
 int pmgk_chaincov_sqnorm_tiles(int32_t n, const double *Sigma, double *partial, void *stream);
 int pmgk_chaincov_reduce(int ntiles, const double *partial, const double *norm, double *out, void *stream);
 
+/* integrated autocorrelation time of many series (kernels_iact.hip): X is n x nseries, series fastest with leading dimension ld;
+   Z (n * nseries doubles) receives the series contiguously and is centred in place by the scan; every sum in an order that
+   (n, lag) alone fixes (the kernel file states it).  One workgroup per series scans the lags in blocks of PMGK_IACT_LAG_BLOCK,
+   one lane per lag, and stops at the block that holds the window: 256 is one wavefront on each SIMD of a compute unit and more
+   than the window of a chain that mixes, so that such a chain costs one block. */
+#define PMGK_IACT_LAG_BLOCK 256
+int pmgk_iact_transpose(int64_t n, int32_t nseries, const double *X, int64_t ld, double *Z, void *stream);
+int pmgk_iact_scan(int64_t n, int32_t nseries, double *Z, int32_t max_lag, int32_t nacf, double *acf, double *tau, int32_t *window, int32_t *valid, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

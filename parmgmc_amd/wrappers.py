@@ -679,6 +679,14 @@ class ChainStats:
         t = self.trace(q, first, count)
         return [iact(t[:, c]) for c in range(self.nchains)]
 
+    def iact_device(self, q: int = 0, first: int = 0, count=None, max_lag: int = 0, nacf: int = 0):
+        """pmg_chainstats_iact: the IACT of every chain's trace of QOI q over the steps [first, first + count), computed where
+        the trace lies.  Returns (tau, window, valid), numpy arrays of one entry per chain, and with nacf > 0 also the
+        autocorrelation as an (nacf, C) device tensor.  max_lag = 0: no limit; see iact_chains."""
+        if count is None:
+            count = max(self.count()[0] - first, 0)
+        return _iact_call(self.nchains, nacf, lambda tau, win, val, acf: lib.pmg_chainstats_iact(self._h, q, first, count, max_lag, tau, win, val, nacf, acf, _stream()))
+
     def destroy(self):
         if self._h:
             check(lib.pmg_chainstats_destroy(C.byref(self._h)))
@@ -822,6 +830,37 @@ def iact(x):
     tau, valid = C.c_double(), C.c_int()
     check(lib.pmg_iact(len(x), x.ctypes.data, C.byref(tau), None, C.byref(valid)))
     return tau.value, bool(valid.value)
+
+
+IACT_LAG_BLOCK = 256  # PMG_IACT_LAG_BLOCK: lags per block of the device scan
+
+
+def _iact_call(nseries: int, nacf: int, call):
+    """the host outputs and the optional acf tensor of the two device IACT entry points around one library call"""
+    tau, window, valid = np.empty(nseries), np.empty(nseries, np.int32), np.empty(nseries, np.int32)
+    acf = None
+    if nacf > 0:
+        import torch
+
+        acf = torch.empty((nacf, nseries), dtype=torch.float64, device="cuda")
+    check(call(tau.ctypes.data, window.ctypes.data, valid.ctypes.data, _ptr(acf) if acf is not None else None))
+    out = (tau, window, valid.astype(bool))
+    return out + (acf,) if acf is not None else out
+
+
+def iact_chains(X, max_lag: int = 0, nacf: int = 0):
+    """pmg_iact_chains: IACT (reference src/iact.c:73-92) of every column of an (n, S) float64 CUDA tensor -- rows are steps,
+    columns are series; a column slice of a wider contiguous tensor is taken where it lies.  Returns (tau, window, valid), numpy
+    arrays of S entries, and with nacf > 0 also the autocorrelation of the first nacf lags as an (nacf, S) device tensor.
+    max_lag = 0: no limit, the reference's rule; max_lag > 0: a series without a window up to max_lag reports window = -1,
+    tau = T_max_lag, valid = False.  Runs on the current stream and synchronises it."""
+    import torch
+
+    assert isinstance(X, torch.Tensor) and X.is_cuda and X.dtype == torch.float64 and X.dim() == 2, "need an (n, S) float64 CUDA tensor"
+    n, S = (int(v) for v in X.shape)
+    assert S == 1 or X.stride(1) == 1, "the series of a step must be adjacent in memory"
+    ld = int(X.stride(0)) if n > 1 else S
+    return _iact_call(S, nacf, lambda tau, win, val, acf: lib.pmg_iact_chains(n, S, C.c_void_p(X.data_ptr()), ld, max_lag, tau, win, val, nacf, acf, _stream()))
 
 
 def estimate_covariance_errors(rowptr, colidx, vals, samples, chains: int):

@@ -10,6 +10,9 @@ build_hierarchy(A, coarse_max=2000), PMG_COLORING_ITERATED, set_smoother(True, 1
 algorithmic bytes 8 n C + 32 n + 8 n nqoi over that time, beside the read-2/write-1 triad (pmg_stream_triad on 4 n C / 3 doubles,
 timed here in the same run) and beside the torch formulation of the same step (s = Y.sum(1); q = ((Y - (s/C)[:, None])**2).sum(1);
 t = w @ Y; the merge on n-vectors); then MGMC chains with and without stats= (the added time per sample beside the update time).
+--stats --iact: after these, per chain count one MGMC chains call of --iact-steps samples with stats= (timed), then on its trace
+ChainStats.iact_device (pmg_chainstats_iact; wall time with the copy of the results) beside ChainStats.iact (the download and
+pmg_iact per chain), their ratio, and the effective samples per second of sampling, sum_c steps / tau_c over the sampling time.
 
 --lowrank K: posterior lines instead, with K ball observations on the mesh vertices (column j = indicator of the vertices
 within --radius of centre j, divided by their count): the MATLRC sweep (mcgibbs, forward; pmg_mcsor_sample_chains on an
@@ -66,6 +69,8 @@ def main():
     ap.add_argument("--radius", type=float, default=0.1)
     ap.add_argument("--matlrc-only", action="store_true", help="with --lowrank: only the MATLRC MGMC chains calls (for runs under rocprofv3)")
     ap.add_argument("--stats", action="store_true", help="the chain-statistics lines (pmg_chainstats_update)")
+    ap.add_argument("--iact", action="store_true", help="with --stats: the IACT of every chain on the device beside the host path, effective samples per second")
+    ap.add_argument("--iact-steps", type=int, default=1000, help="with --iact: steps of the MGMC chains call whose trace is analysed")
     ap.add_argument("--cov", action="store_true", help="the covariance-error lines (pmg_chaincov_update)")
     ap.add_argument("--cov-updates-only", action="store_true", help="with --cov: only the update groups (for runs under rocprofv3)")
     args = ap.parse_args()
@@ -216,6 +221,57 @@ def stats_lines(args, n, mg, b):
         print(json.dumps({"chains": C, "its": its, "mgmc_ms_per_sample": plain[0] / its, "mgmc_spread_ms_per_sample": [plain[1] / its, plain[2] / its],
                           "mgmc_stats_ms_per_sample": with_stats[0] / its, "mgmc_stats_spread_ms_per_sample": [with_stats[1] / its, with_stats[2] / its],
                           "added_us_per_sample": (with_stats[0] - plain[0]) / its * 1e3, "steps_recorded": cs.count()[0]}), flush=True)
+        del Y, cs
+        torch.cuda.empty_cache()
+    if args.iact:
+        iact_lines(args, n, mg, b, w)
+
+
+def wall_ms(fn, regions):
+    """median wall time in ms of fn(), which returns with its results on the host; one warm-up call first"""
+    fn()
+    ms = []
+    for _ in range(regions):
+        t0 = time.perf_counter()
+        fn()
+        ms.append((time.perf_counter() - t0) * 1e3)
+    return sorted(ms)[len(ms) // 2]
+
+
+def iact_lines(args, n, mg, b, w):
+    """one MGMC chains call of --iact-steps samples with stats= (timed), then on its trace: ChainStats.iact_device (wall time, the
+    copy of the results included) beside ChainStats.iact (the download and pmg_iact per chain), and the effective samples per
+    second of sampling, sum_c steps / tau_c over the sampling time"""
+    import numpy as np
+    import torch
+
+    from parmgmc_amd import IACT_LAG_BLOCK, ChainStats
+
+    steps = args.iact_steps
+    for C in args.chains:
+        if C < 2:
+            continue
+        seeds = [0xCAFE + 7919 * c for c in range(C)]
+        Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+        cs = ChainStats(n, C, [w], max_steps=steps)
+        mg.sample_chains(b, Y, 2, seeds)  # first-use workspace
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        mg.sample_chains(b, Y, steps, seeds, stats=cs)
+        torch.cuda.synchronize()
+        sample_s = time.perf_counter() - t0
+        dev_ms = wall_ms(lambda: cs.iact_device(0), args.regions)
+        host_ms = wall_ms(lambda: cs.iact(0), args.regions)
+        tau, window, valid = cs.iact_device(0)
+        hosted = cs.iact(0)
+        ok = np.isfinite(tau) & (tau > 0)
+        ess = float((steps / tau[ok]).sum())
+        print(json.dumps({"chains": C, "steps_recorded": cs.count()[0], "sampling_s": sample_s, "chain_samples_per_s": C * steps / sample_s,
+                          "iact_device_ms": dev_ms, "iact_host_ms": host_ms, "host_over_device": host_ms / dev_ms,
+                          "tau_min_median_max": [float(np.min(tau)), float(np.median(tau)), float(np.max(tau))], "window_max": int(window.max()), "chains_valid": int(valid.sum()),
+                          "max_abs_tau_device_minus_host": float(np.max(np.abs(tau - np.array([t for t, _ in hosted])))),
+                          "multiply_adds_model": float(steps) * float((window.astype(np.int64) // IACT_LAG_BLOCK + 1).sum()) * IACT_LAG_BLOCK,
+                          "effective_samples": ess, "effective_samples_per_s": ess / sample_s}), flush=True)
         del Y, cs
         torch.cuda.empty_cache()
 
