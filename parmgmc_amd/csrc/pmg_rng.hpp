@@ -269,6 +269,33 @@ __device__ __forceinline__ void normal_pair_fill(uint32_t c0, uint32_t c1, uint3
   z1 = radius * s;
 }
 
+// Two Box-Muller pairs, from the Philox blocks of the counters (c0, c1a, c2, c3) and (c0, c1b, c2, c3), behind ONE deferred
+// table fill: a wavefront that owns two grid rows pays the exchange through LDS and the constants once.  Each pair goes
+// through the operations of normal_pair_fill one by one, so its bits are those of a call of its own; the two chains do
+// not depend on each other and the scheduler interleaves them.
+__device__ __forceinline__ void normal_pair_fill2(uint32_t c0, uint32_t c1a, uint32_t c1b, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, LogTabEntry entry, LogTabEntry *wave_tab, int lane, const RngConsts &K, double &za0, double &za1, double &zb0, double &zb1)
+{
+  const Philox4 pa = philox4x32_10(c0, c1a, c2, c3, k0, k1), pb = philox4x32_10(c0, c1b, c2, c3, k0, k1);
+  uint32_t      xalo, xahi, yalo, yahi, xblo, xbhi, yblo, ybhi;
+  u53_int(pa.r0, pa.r1, xalo, xahi);
+  u53_int(pa.r2, pa.r3, yalo, yahi);
+  u53_int(pb.r0, pb.r1, xblo, xbhi);
+  u53_int(pb.r2, pb.r3, yblo, ybhi);
+  double sa, ca, sb, cb;
+  sincos_turns(yalo, yahi, K, sa, ca);
+  sincos_turns(yblo, ybhi, K, sb, cb);
+  const RngLogConsts KL = load_log_consts();
+  wave_tab[lane]        = entry;
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const double ra = sqrt_pos(minus2_log_u(xalo, xahi, wave_tab, KL)), rb = sqrt_pos(minus2_log_u(xblo, xbhi, wave_tab, KL));
+  za0 = ra * ca;
+  za1 = ra * sa;
+  zb0 = rb * cb;
+  zb1 = rb * sb;
+}
+
 __device__ __forceinline__ void normal_pair(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, const LogTabEntry *tab, double &z0, double &z1)
 {
   const Philox4 p = philox4x32_10(c0, c1, c2, c3, k0, k1);
