@@ -5,6 +5,11 @@ class-stencil lines with a packed x remainder, 2-D and semicoarsened levels (no 
 Q1 transfers), even extents on the coarsest levels and minimal extents -- under the settings that select the
 one-colour prolongation (omega = 1: forward, backward and symmetric skip different colours) and those that do not.
 
+The class-stencil levels of these shapes have lines of 2^k + 1 points (and 144) and at most 5 or 8 m + 1 lines; the other ways
+a class-stencil line is cut into wavefronts (a full segment, an unpacked remainder behind one, both sides of the pack
+threshold, a remainder of one pair) and the other positions of a plane's last line tile are the shapes of st27_splits.py
+(SHAPES, VCYCLE_SHAPES), run kernel by kernel and as whole V-cycles in test_gpu_st27_splits.py.
+
 Every sample of a 3-sample chain is compared, at the relative max-norm tolerance of test_gpu_mgmc.py (1e-11: Galerkin
 entries and residual sums are taken in another order).  The negative control shifts one level's noise counter in the
 oracle and requires the sampler to be far outside that tolerance: every level's contribution is visible."""
