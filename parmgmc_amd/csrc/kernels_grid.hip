@@ -421,85 +421,135 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void grid
 // for bit) and two non-temporal stores.  Planes are paired by launch-local index, parities come from the global plane.
 // An odd plane count leaves the last pair without k1: wave-uniformly, its second-plane rows fall back on the first
 // plane's (valid) addresses and its second store is suppressed.
+// The FRONT -- what a wavefront executes before its first streaming load -- is kept short, because a wavefront holds a
+// slot of its SIMD through it without a byte in flight:
+//   * every launch constant the front reads sits in ONE argument block (grid_pair_launch, filled at the launch site) in
+//     front of the pointers: one scalar-load round trip, where the layout, the scalars and the pointers took three;
+//   * ONE scalar base per array -- row j of plane k0 - 1, the lowest row the wavefront can touch -- and a wave-uniform
+//     unsigned 32-bit byte offset per row (one v_add_u32 with a scalar operand each; the clamps select between offsets)
+//     instead of thirteen 64-bit row pointers with their clamps, which did not fit the scalar registers.  The launch site
+//     keeps the one-plane kernel where the offsets (up to 3 sp + 2 sx doubles) do not fit 32 bits;
+//   * everything that only the row updates need stands behind the last request: the operator-table entries and the store
+//     base with the generator's constants, the x flags and the clamped coefficients behind the generator;
+//   * the flat walk's w / nl is a multiply-high by a reciprocal from the launch site.
+// Left to the compiler this takes 77 vector registers and no scalar register parked in lanes (83 and 34 before), and with
+// them six wavefronts per SIMD -- which this kernel does not want: measured at 512^3, six take 2.6 % longer than five, five
+// 3 % longer than four, and three 3 % longer than four again, so the kernel is pinned to four (amdgpu_waves_per_eu).  DESIGN
+// section 3 has the numbers of every step.
+struct grid_pair_launch {
+  int32_t  nx, ny, sx, kz0, nzg; // of the layout
+  int32_t  c, kbegin, kcount, npair;
+  int32_t  bandw;                // lines per XCD band (0: plain (x, y, z) launch)
+  int32_t  flat;                 // != 0: the flat walk; then 4 * gridDim.y
+  int32_t  thr;                  // flat walk: the bands xcd >= thr hold bandw + 1 lines
+  uint32_t mul0, mul1;           // ceil(2^32 / bandw), ceil(2^32 / (bandw + 1)): w / nl = mulhi(w, mul) for w * nl < 2^32
+  uint32_t sp8, sx8;             // plane and line stride in bytes
+};
+
 template <bool OMEGA1>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96))) void grid_color_pair_sweep_kernel(pmgk_grid_layout L, pmgk_grid_op op, int c, int zmain, int bandw, int kbegin, int kcount, const double *__restrict__ b_own, const double *__restrict__ y_other, double *__restrict__ y_own)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_sgpr(96), amdgpu_waves_per_eu(4, 4))) void grid_color_pair_sweep_kernel(grid_pair_launch P, const double *__restrict__ b_own, const double *__restrict__ y_other, double *__restrict__ y_own, pmgk_grid_op op)
 {
   const int ty = __builtin_amdgcn_readfirstlane(threadIdx.y);
   __shared__ pmg::LogTabEntry s_logtab[4 * PMG_LOGTAB_SIZE];
   pmg::LogTabEntry           *tab       = s_logtab + ty * PMG_LOGTAB_SIZE;
   const d2                    tab_e     = ld2(reinterpret_cast<const double *>(pmg::g_logtab + threadIdx.x));
   const pmg::LogTabEntry      tab_entry = {tab_e.x, tab_e.y};
-  const int npair = (kcount + 1) >> 1;
-  int       t, j, kz = (int)blockIdx.z;
-  grid_thread_position<false>(0, bandw, ty, t, j);
-  if (zmain > 0) { // the FLAT walk of grid_color_sweep_kernel over (plane pair, line) runs
-    const int xcd = (int)(blockIdx.x & 7u), extra = max(xcd - (8 - (L.ny - 8 * bandw)), 0);
-    const int first = xcd * bandw + extra, nl = bandw + (xcd >= 8 - (L.ny - 8 * bandw) ? 1 : 0);
-    const int w     = ((int)blockIdx.y + (int)gridDim.y * (int)blockIdx.z) * 4 + ty;
-    if (nl <= 0) return;
-    kz = w / nl;
-    t  = (int)(blockIdx.x >> 3) * 64 + (int)threadIdx.x;
+  asm volatile("" ::"s"(P.sp8), "s"(P.sx8), "s"(b_own), "s"(y_other), "s"(op.key0), "s"(op.key1), "s"(op.sweep)); // the strides and pointers are fetched with the decode's scalars, not behind it
+  const int xcd = (int)(blockIdx.x & 7u);
+  int       bx, j, kz;
+  if (P.flat) { // the FLAT walk of grid_color_sweep_kernel over (plane pair, line) runs
+    const int  over  = xcd - P.thr;
+    const int  first = xcd * P.bandw + max(over, 0), nl = P.bandw + (over >= 0 ? 1 : 0);
+    const int  w     = ((int)blockIdx.y * 4 + P.flat * (int)blockIdx.z) + ty;
+    kz = (int)__umulhi((uint32_t)w, over >= 0 ? P.mul1 : P.mul0);
+    bx = (int)(blockIdx.x >> 3);
     j  = first + (w - kz * nl);
+  } else {
+    const int jl = (int)blockIdx.y * 4 + ty;
+    bx = P.bandw > 0 ? (int)(blockIdx.x >> 3) : (int)blockIdx.x;
+    j  = P.bandw > 0 ? (jl < P.bandw ? xcd * P.bandw + jl : 0x40000000) : jl;
+    kz = (int)blockIdx.z;
   }
-  if (j >= L.ny || kz >= npair) return; // whole wavefront: lines behind a band, the last z layers of the shorter bands
+  if (j >= P.ny || kz >= P.npair) return; // whole wavefront: lines behind a band, the last z layers of the shorter bands
 
-  const bool pair = 2 * kz + 1 < kcount;
-  const int  k0 = kbegin + 2 * kz, kg0 = k0 + L.kz0, kg1 = kg0 + (pair ? 1 : 0);
-  const int  p0 = (c + j + kg0) & 1, p1 = (c + j + kg1) & 1;
-  const bool inrow = 2 * t < L.sx, live0 = inrow && 4 * t + p0 < L.nx, live1 = pair && inrow && 4 * t + p1 < L.nx;
+  const bool pair = 2 * kz + 1 < P.kcount;
+  const int  k0 = P.kbegin + 2 * kz, kg0 = k0 + P.kz0, kg1 = kg0 + (pair ? 1 : 0);
+  const int  p0 = (P.c + j + kg0) & 1, p1 = (P.c + j + kg1) & 1;
+  int        t  = bx * 64 + (int)threadIdx.x;
+  const bool inrow = 2 * t < P.sx, live0 = inrow && 4 * t + p0 < P.nx, live1 = pair && inrow && 4 * t + p1 < P.nx;
   const bool live = live0 || live1;
   // every lane stays for the table exchange: a lane without a point moves to t = 0 and only its stores are suppressed
   if (!__builtin_amdgcn_ballot_w64(live)) return;
   t = live ? t : 0;
-  const int  i00 = 4 * t + p0, i01 = i00 + 2, i10 = 4 * t + p1, i11 = i10 + 2;
-  const bool hasS = j > 0, hasN = j < L.ny - 1, hasD0 = kg0 > 0, hasU0 = kg0 < L.nzg - 1, hasD1 = kg1 > 0, hasU1 = kg1 < L.nzg - 1;
-  const double   h2   = op.h2;
-  const int64_t  row0 = (int64_t)(k0 + 1) * L.sp + (int64_t)j * L.sx, dk = pair ? L.sp : 0;
+  const bool hasS = j > 0, hasN = j < P.ny - 1, hasD0 = kg0 > 0, hasU0 = kg0 < P.nzg - 1, hasU1 = kg1 < P.nzg - 1;
+  // byte offsets from row (k0 - 1, j): rows k0 and k1, then the clamped neighbour rows -- all wave-uniform and >= 0
+  const uint32_t sp8 = P.sp8, sx8 = P.sx8, dS = hasS ? sx8 : 0u, dN = hasN ? sx8 : 0u;
+  const uint32_t d0 = sp8, d1 = sp8 + (pair ? sp8 : 0u);
+  const uint64_t rowm = (uint64_t)(uint32_t)k0 * sp8 + (uint32_t)j * sx8;
+  const char    *yo   = reinterpret_cast<const char *>(y_other) + rowm, *bo = reinterpret_cast<const char *>(b_own) + rowm;
   const uint32_t lo   = 16u * (uint32_t)t;
-  const double  *yo0 = y_other + row0, *yo1 = yo0 + dk;
-  const int      eo0 = p0 ? (2 * t + 2 < L.sx ? 2 : 1) : (t > 0 ? -1 : 0), eo1 = p1 ? (2 * t + 2 < L.sx ? 2 : 1) : (t > 0 ? -1 : 0);
-  const int      nyz0 = min(j, 1) + min(L.ny - 1 - j, 1) + min(kg0, 1) + min(L.nzg - 1 - kg0, 1);
-  const int      nyz1 = min(j, 1) + min(L.ny - 1 - j, 1) + min(kg1, 1) + min(L.nzg - 1 - kg1, 1);
+  const uint32_t v0 = lo + d0, v1 = lo + d1;
+  // x edge value: p = 0: m' = 2t - 1, p = 1: m' = 2t + 2, clamped to the row
+  const uint32_t eW = t > 0 ? (uint32_t)-8 : 0u, eE = 2 * t + 2 < P.sx ? 16u : 8u;
+  const uint32_t m0 = (uint32_t)-p0, m1 = (uint32_t)-p1; // wave-uniform masks: no branch on the parity
+  const uint32_t e0 = (eE & m0) | (eW & ~m0), e1 = (eE & m1) | (eW & ~m1);
+  // same-line rows k0-1, k0, k1, k1+1: rB is Vc of plane k0 and D of plane k1, rC is U of plane k0 and Vc of plane k1
+  const double *yod = reinterpret_cast<const double *>(yo), *bod = reinterpret_cast<const double *>(bo);
+  d2     rA  = ld2(at_bytes(yod, lo + (hasD0 ? 0u : sp8)));
+  d2     rB  = ld2(at_bytes(yod, v0));
+  d2     rC  = ld2(at_bytes(yod, v0 + (hasU0 ? sp8 : 0u)));
+  d2     rE  = ld2(at_bytes(yod, v1 + (hasU1 ? sp8 : 0u)));
+  double ed0 = *at_bytes(yod, v0 + e0);
+  double ed1 = *at_bytes(yod, v1 + e1);
+  d2     oS0 = ld2(at_bytes(yod, lo + (d0 - dS)));
+  d2     oN0 = ld2(at_bytes(yod, lo + (d0 + dN)));
+  d2     oS1 = ld2(at_bytes(yod, lo + (d1 - dS)));
+  d2     oN1 = ld2(at_bytes(yod, lo + (d1 + dN)));
+#ifndef PMG_GRID_NO_NT
+  d2     bb0 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(bod, v0)));
+  d2     bb1 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(bod, v1)));
+#else
+  d2     bb0 = ld2(at_bytes(bod, v0));
+  d2     bb1 = ld2(at_bytes(bod, v1));
+#endif
+  __builtin_amdgcn_sched_barrier(0); // all thirteen requests go out before anything else starts
+  // ... and nothing that follows is computed in front of them: what the generator and the row updates read (the line, the
+  // planes, the operator's scalars) passes through an empty statement behind the barrier, or instruction selection places
+  // the key schedule and the wait for the operator's scalar loads in front of the requests
+  int      jr = j, kr0 = kg0, kr1 = kg1;
+  uint32_t key0 = op.key0, key1 = op.key1, sweep_lo = (uint32_t)op.sweep, sweep_hi = (uint32_t)(op.sweep >> 32);
+  asm volatile("" : "+s"(jr), "+s"(kr0), "+s"(kr1), "+s"(key0), "+s"(key1), "+s"(sweep_lo), "+s"(sweep_hi));
+  const pmg::RngConsts K = pmg::load_sincos_consts();
+  // what only the row updates need: fetched with the generator's constants, waited for behind the Philox rounds
+  const int      nyz0 = min(jr, 1) + min(P.ny - 1 - jr, 1) + min(kr0, 1) + min(P.nzg - 1 - kr0, 1);
+  const int      nyz1 = min(jr, 1) + min(P.ny - 1 - jr, 1) + min(kr1, 1) + min(P.nzg - 1 - kr1, 1);
   const double   idA0 = uniform(op.idiag[nyz0 + 1]), idB0 = uniform(op.idiag[nyz0 + 2]), idA1 = uniform(op.idiag[nyz1 + 1]), idB1 = uniform(op.idiag[nyz1 + 2]);
   const double   sqA0 = uniform(op.sqrtdiag[nyz0 + 1]), sqB0 = uniform(op.sqrtdiag[nyz0 + 2]);
   const double   sqA1 = uniform(op.sqrtdiag[nyz1 + 1]), sqB1 = uniform(op.sqrtdiag[nyz1 + 2]);
-  double        *out0 = y_own + row0, *out1 = out0 + dk;
-  // same-line rows k0-1, k0, k1, k1+1: rB is Vc of plane k0 and D of plane k1, rC is U of plane k0 and Vc of plane k1
-  d2     rA  = ld2(at_bytes(yo0 - (hasD0 ? L.sp : 0), lo));
-  d2     rB  = ld2(at_bytes(yo0, lo));
-  d2     rC  = ld2(at_bytes(yo0 + (hasU0 ? L.sp : 0), lo));
-  d2     rE  = ld2(at_bytes(yo1 + (hasU1 ? L.sp : 0), lo));
-  double ed0 = *at_bytes(yo0, lo + 8u * (uint32_t)eo0);
-  double ed1 = *at_bytes(yo1, lo + 8u * (uint32_t)eo1);
-  d2     oS0 = ld2(at_bytes(yo0 - (hasS ? L.sx : 0), lo));
-  d2     oN0 = ld2(at_bytes(yo0 + (hasN ? L.sx : 0), lo));
-  d2     oS1 = ld2(at_bytes(yo1 - (hasS ? L.sx : 0), lo));
-  d2     oN1 = ld2(at_bytes(yo1 + (hasN ? L.sx : 0), lo));
-#ifndef PMG_GRID_NO_NT
-  d2     bb0 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(b_own + row0, lo)));
-  d2     bb1 = __builtin_nontemporal_load(reinterpret_cast<const d2 *>(at_bytes(b_own + row0 + dk, lo)));
-#else
-  d2     bb0 = ld2(at_bytes(b_own + row0, lo));
-  d2     bb1 = ld2(at_bytes(b_own + row0 + dk, lo));
-#endif
-  __builtin_amdgcn_sched_barrier(0); // all thirteen requests go out before the generator starts
-  const pmg::RngConsts K = pmg::load_sincos_consts();
+  double        *out = reinterpret_cast<double *>(reinterpret_cast<char *>(y_own) + rowm);
   __builtin_amdgcn_sched_barrier(0);
   // both draws while the loads are in flight: nothing below may touch a loaded value before the four normals exist
   double z00, z01, z10, z11;
-  pmg::normal_pair_fill2((uint32_t)t, (uint32_t)(j + (int64_t)L.ny * kg0), (uint32_t)(j + (int64_t)L.ny * kg1), (uint32_t)op.sweep, ((uint32_t)(op.sweep >> 32) & 0x7fffffffu) | ((uint32_t)c << 31), op.key0, op.key1, tab_entry, tab, (int)threadIdx.x, K, z00, z01, z10, z11);
+  pmg::normal_pair_fill2((uint32_t)t, (uint32_t)(jr + (int64_t)P.ny * kr0), (uint32_t)(jr + (int64_t)P.ny * kr1), sweep_lo, (sweep_hi & 0x7fffffffu) | ((uint32_t)P.c << 31), key0, key1, tab_entry, tab, (int)threadIdx.x, K, z00, z01, z10, z11);
   asm volatile("" : "+v"(rA.x), "+v"(rA.y), "+v"(rB.x), "+v"(rB.y), "+v"(rC.x), "+v"(rC.y), "+v"(rE.x), "+v"(rE.y), "+v"(ed0), "+v"(ed1) : "v"(z00), "v"(z01), "v"(z10), "v"(z11));
   asm volatile("" : "+v"(oS0.x), "+v"(oS0.y), "+v"(oN0.x), "+v"(oN0.y), "+v"(oS1.x), "+v"(oS1.y), "+v"(oN1.x), "+v"(oN1.y), "+v"(bb0.x), "+v"(bb0.y), "+v"(bb1.x), "+v"(bb1.y) : "v"(z00), "v"(z01), "v"(z10), "v"(z11));
-  const bool hasW00 = i00 > 0, hasE00 = i00 < L.nx - 1, hasE01 = i01 < L.nx - 1, hasW10 = i10 > 0, hasE10 = i10 < L.nx - 1, hasE11 = i11 < L.nx - 1;
-  const d2 r0 = grid_row_update<true, OMEGA1>(op, p0, hasW00, hasE00, hasE01, i01 < L.nx, hasS, hasN, hasD0, hasU0, h2, hasW00 && hasE00, hasE01, idA0, idB0, sqA0, sqB0, rB, ed0, oS0, oN0, rA, rC, bb0, z00, z01, out0, lo);
-  const d2 r1 = grid_row_update<true, OMEGA1>(op, p1, hasW10, hasE10, hasE11, i11 < L.nx, hasS, hasN, hasD1, hasU1, h2, hasW10 && hasE10, hasE11, idA1, idB1, sqA1, sqB1, rC, ed1, oS1, oN1, rB, rE, bb1, z10, z11, out1, lo);
-  asm volatile("" ::"v"(r0.x), "v"(r0.y), "v"(r1.x), "v"(r1.y), "s"(out0)); // the computation stays in front of the exits
+  // the x flags and the clamped coefficients are formed here, behind the generator, which has no scalar register to spare
+  int    tr = t;
+  double h2 = op.h2;
+  asm volatile("" : "+v"(tr), "+s"(h2), "+s"(jr), "+s"(kr0), "+s"(kr1) : "v"(z00), "v"(z01), "v"(z10), "v"(z11));
+  const bool uS = jr > 0, uN = jr < P.ny - 1, uD0 = kr0 > 0, uU0 = kr0 < P.nzg - 1, uD1 = kr1 > 0, uU1 = kr1 < P.nzg - 1;
+  const int  q0 = (P.c + jr + kr0) & 1, q1 = (P.c + jr + kr1) & 1;
+  const int  i00 = 4 * tr + q0, i01 = i00 + 2, i10 = 4 * tr + q1, i11 = i10 + 2;
+  const bool hasW00 = i00 > 0, hasE00 = i00 < P.nx - 1, hasE01 = i01 < P.nx - 1, hasW10 = i10 > 0, hasE10 = i10 < P.nx - 1, hasE11 = i11 < P.nx - 1;
+  const d2 r0 = grid_row_update<true, OMEGA1>(op, q0, hasW00, hasE00, hasE01, i01 < P.nx, uS, uN, uD0, uU0, h2, hasW00 && hasE00, hasE01, idA0, idB0, sqA0, sqB0, rB, ed0, oS0, oN0, rA, rC, bb0, z00, z01, out, v0);
+  const d2 r1 = grid_row_update<true, OMEGA1>(op, q1, hasW10, hasE10, hasE11, i11 < P.nx, uS, uN, uD1, uU1, h2, hasW10 && hasE10, hasE11, idA1, idB1, sqA1, sqB1, rC, ed1, oS1, oN1, rB, rE, bb1, z10, z11, out, v1);
+  asm volatile("" ::"v"(r0.x), "v"(r0.y), "v"(r1.x), "v"(r1.y), "s"(out)); // the computation stays in front of the exits
 #ifndef PMG_GRID_NO_NT
-  if (live0) __builtin_nontemporal_store(r0, reinterpret_cast<d2 *>(at_bytes(out0, lo)));
-  if (live1) __builtin_nontemporal_store(r1, reinterpret_cast<d2 *>(at_bytes(out1, lo)));
+  if (live0) __builtin_nontemporal_store(r0, reinterpret_cast<d2 *>(at_bytes(out, v0)));
+  if (live1) __builtin_nontemporal_store(r1, reinterpret_cast<d2 *>(at_bytes(out, v1)));
 #else
-  if (live0) *reinterpret_cast<d2 *>(at_bytes(out0, lo)) = r0;
-  if (live1) *reinterpret_cast<d2 *>(at_bytes(out1, lo)) = r1;
+  if (live0) *reinterpret_cast<d2 *>(at_bytes(out, v0)) = r0;
+  if (live1) *reinterpret_cast<d2 *>(at_bytes(out, v1)) = r1;
 #endif
 }
 
@@ -887,6 +937,7 @@ struct grid_mapping {
 
 static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, bool allow_tail, bool allow_flat = false, bool allow_pair = false)
 {
+  const int kcount_planes = kcount;
   static int banded_env = -1, tail_env = -1, flat_env = -1, pair_env = -1;
   if (banded_env < 0) {
     const char *e = getenv("PMG_GRID_BANDED");
@@ -933,7 +984,35 @@ static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, b
     M.grid = dim3(gx, gy, zlayers + M.ztail);
   }
   if (!M.tail) M.tmain = M.tailw = 0;
+  // the pair kernel addresses its rows by unsigned 32-bit byte offsets of up to 3 sp + 2 sx doubles from one base per array,
+  // and divides the flat walk's index by a 32-bit reciprocal, exact while index * (lines per band) < 2^32: a grid beyond
+  // either keeps the one-plane kernel
+  if (M.pair && (8 * (3 * L->sp + 2 * (int64_t)L->sx) >= ((int64_t)1 << 32) || (M.zmain > 0 && (M.bandw < 2 || 4 * (int64_t)M.grid.y * M.grid.z * (M.bandw + 1) >= ((int64_t)1 << 32)))))
+    return grid_choose_mapping(L, kcount_planes, allow_tail, allow_flat, false);
   return M;
+}
+
+// the launch constants of grid_color_pair_sweep_kernel, decoded once here instead of by every wavefront
+static grid_pair_launch grid_pair_constants(const grid_mapping &M, const pmgk_grid_layout &L, int color, int kbegin, int kcount)
+{
+  grid_pair_launch P;
+  P.nx     = L.nx;
+  P.ny     = L.ny;
+  P.sx     = L.sx;
+  P.kz0    = L.kz0;
+  P.nzg    = L.nzg;
+  P.c      = color;
+  P.kbegin = kbegin;
+  P.kcount = kcount;
+  P.npair  = (kcount + 1) >> 1;
+  P.bandw  = M.bandw;
+  P.flat   = M.zmain > 0 ? 4 * (int)M.grid.y : 0;
+  P.thr    = 8 - (L.ny - 8 * M.bandw);
+  P.mul0   = M.zmain > 0 ? (uint32_t)((((uint64_t)1 << 32) + M.bandw - 1) / M.bandw) : 0u;
+  P.mul1   = M.zmain > 0 ? (uint32_t)((((uint64_t)1 << 32) + M.bandw) / (M.bandw + 1)) : 0u;
+  P.sp8    = (uint32_t)(8 * L.sp);
+  P.sx8    = 8u * (uint32_t)L.sx;
+  return P;
 }
 
 template <bool NOISY, bool OMEGA1, bool HALO>
@@ -944,7 +1023,7 @@ static void launch_sweep(const grid_mapping &M, dim3 block, hipStream_t s, const
   else {
     if constexpr (NOISY && !HALO) {
       if (M.pair) {
-        hipLaunchKernelGGL((grid_color_pair_sweep_kernel<OMEGA1>), M.grid, block, 0, s, L, op, color, M.zmain, M.bandw, kbegin, kcount, bo, yo, ys);
+        hipLaunchKernelGGL((grid_color_pair_sweep_kernel<OMEGA1>), M.grid, block, 0, s, grid_pair_constants(M, L, color, kbegin, kcount), bo, yo, ys, op);
         return;
       }
     }
