@@ -3,7 +3,7 @@
 // Replace the dense PETSc products of the reference: MatMultTranspose(B, y, w) / MatMult(Bb, w, z) / VecAXPY in
 // MCSORPostSOR_LRC (src/mc_sor.c:101-112) and PCSORGibbsSample (src/pc_sorgibbs.c:97-101), MatMultAdd(B, wk, w, w)
 // in PrepareRHS_LRC (src/pc_mcgibbs.c:130-140, src/pc_sorgibbs.c:86-90), and MatMatMult(C, Sb) of
-// MCSORBuildLRCCorrection (src/mc_sor.c:535).  1 <= k <= 64 (tested at 1, 8, 9, 33, 64; the LDS arrays hold 64 columns):
+// MCSORBuildLRCCorrection (src/mc_sor.c:535).  1 <= k <= 64 (tested at 1, 2, 3, 4, 5, 8, 9, 17, 33, 63, 64; the LDS arrays hold 64 columns):
 // every kernel streams the N x k matrix once, column-major with leading dimension ld, rows in the sampler's storage layout --
 // 8 N k bytes, HBM bound.
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-"""Workloads of tests/test_gpu_mgmc_lowrank_chains.py: MGMC hierarchies with a low-rank (MATLRC) update for the many-chains
+"""Workloads of tests/test_gpu_mgmc_lowrank_chains.py and tests/test_gpu_chain_lane_splits.py: MGMC hierarchies with a low-rank (MATLRC) update for the many-chains
 V-cycle.  The observation recipes are those of tests/test_gpu_lowrank_chains.py (copied: that module is a test file), the
 delay / stream-pair helpers those of tests/test_gpu_stream_contract.py; the byte formula restates the comment of
 pmg_mgmc_get_algorithmic_bytes_chains."""
@@ -212,3 +212,28 @@ def streams(delay):
         if concurrent:
             return side, third
     pytest.fail("no two streams of this process run concurrently")
+
+
+# ---- a small hierarchy with BOTH compact chain kernels (tests/test_gpu_chain_lane_splits.py) ------------------------------------
+LSHAPE3_BALLS = {3: (LSHAPE_BALLS, 0.2), 5: (LSHAPE_BALLS + [(1.0, 0.5), (0.5, 1.0)], 0.15)}  # k: (centres inside the L, radius)
+_LSHAPE3 = []
+
+
+def lshape3(k):
+    """lshape.msh refined 3 times (23 809 vertices), P1 kappa^2 M + K, the aggregation hierarchy with coarse_max = 500 (four
+    levels), and k ball observations whose joint support is several 1024-row blocks on the fine level, below a quarter of its
+    rows (the row-compact form), and one block or less further down: (A, ops, ps, B, S)"""
+    from parmgmc_amd.unstructured import assemble_p1, ball_observations, build_hierarchy, read_gmsh41_triangles, refine_uniform
+
+    if not _LSHAPE3:
+        xy, tris = read_gmsh41_triangles(GOLD / "lshape.msh")
+        for _ in range(3):
+            xy, tris = refine_uniform(xy, tris)
+        A = assemble_p1(xy, tris, 1.0)
+        _LSHAPE3.append((xy, A) + tuple(build_hierarchy(A, coarse_max=500)))
+    xy, A, ops, ps = _LSHAPE3[0]
+    centres, radius = LSHAPE3_BALLS[k]
+    B = ball_observations(xy, centres, radius)
+    support = int((B != 0).any(1).sum())
+    assert 2 * ROWS_PER_BLOCK < support < A.shape[0] // 5, support
+    return A, ops, ps, B, np.linspace(40.0, 80.0, k)

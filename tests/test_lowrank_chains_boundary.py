@@ -1,7 +1,8 @@
 """Posterior sampling on many chains: the per-chain right-hand-side entry points (pmg_mcsor_sample_chains_rhs,
 pmg_mgmc_sample_chains_rhs) and the Woodbury chain calls (pmg_woodbury_noisy_rhs_chains, pmg_woodbury_correct_chains) are
-exported, declared, and reject bad calls before any device work.  CPU only: every call here returns before the device is
-touched."""
+exported, declared, and reject bad calls before any device work; so do pmg_woodbury_create's argument checks and the null
+handles of every other pmg_woodbury_* call.  CPU only: every call here returns before the device is touched.  (The state
+checks of a Woodbury handle need one, which lives on the device: tests/test_gpu_woodbury_term.py.)"""
 import ctypes as C
 
 import numpy as np
@@ -90,3 +91,39 @@ def test_woodbury_chains_reject_a_null_handle():
     b, W = C.c_void_p(0x1000), C.c_void_p(0x2000)
     assert lib.pmg_woodbury_noisy_rhs_chains(None, 3, seeds.ctypes.data, 0, b, W, None) == ARG_NULL
     assert lib.pmg_woodbury_correct_chains(None, 3, W, None) == ARG_NULL
+
+
+def _wb_create(n, k, B, ldb, S, out=True):
+    h = C.c_void_p()
+    st = lib.pmg_woodbury_create(n, k, B, ldb, S, None, C.byref(h) if out else None)
+    assert st != 0 and not h.value  # every call here is refused: no handle comes back
+    return st, h
+
+
+def test_woodbury_create_rejects_bad_arguments_before_device_work():
+    B = np.ones((4, 2), order="F")
+    S = np.array([30.0, 40.0])
+    Bp, Sp = B.ctypes.data, S.ctypes.data
+    for k in (0, -1, 65):
+        assert _wb_create(4, k, Bp, 4, Sp)[0] == ARG_OUTOFRANGE, k
+        assert b"rank k" in lib.pmg_last_error_string()
+    assert _wb_create(4, 2, Bp, 3, Sp)[0] == ARG_OUTOFRANGE  # ldb < n
+    assert b"leading dimension 3" in lib.pmg_last_error_string()
+    assert _wb_create(-1, 2, Bp, 4, Sp)[0] == ARG_OUTOFRANGE
+    assert _wb_create(4, 2, None, 4, Sp)[0] == ARG_NULL  # null B with n > 0
+    assert _wb_create(4, 2, Bp, 4, None)[0] == ARG_NULL
+    assert _wb_create(4, 2, Bp, 4, Sp, out=False)[0] == ARG_NULL
+    assert _wb_create(0, 2, None, 0, None)[0] == ARG_NULL  # n = 0 may come without B, not without S
+
+
+def test_woodbury_calls_reject_a_null_handle():
+    p, q = C.c_void_p(0x1000), C.c_void_p(0x2000)
+    bc, cc = C.c_void_p(), C.c_void_p()
+    assert lib.pmg_woodbury_column(None, 0, C.byref(bc), C.byref(cc), None) == ARG_NULL
+    assert lib.pmg_woodbury_set_c_column(None, 0, p, None) == ARG_NULL
+    assert lib.pmg_woodbury_finish(None) == ARG_NULL
+    assert lib.pmg_woodbury_noisy_rhs(None, p, q, 1, 2, None) == ARG_NULL
+    assert lib.pmg_woodbury_correct(None, p, None) == ARG_NULL
+    assert lib.pmg_woodbury_get_correction(None, p) == ARG_NULL
+    h = C.c_void_p()
+    assert lib.pmg_woodbury_destroy(C.byref(h)) == 0 and lib.pmg_woodbury_destroy(None) == 0
