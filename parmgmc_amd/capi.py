@@ -12,6 +12,12 @@ SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP, SOR_SYMMETRIC_SWEEP = 1, 2, 3
 COLORING_GREEDY, COLORING_LEXLEVELS, COLORING_USER, COLORING_ITERATED = 0, 1, 2, 3
 
 
+def directions(sweep_type: int) -> tuple[int, ...]:
+    """The directional sweeps of one sample, each with a fresh draw: symmetric = forward, then backward (reference
+    src/pc_mcgibbs.c:172-181).  The schedule the library keeps in pmg_sweep_iter (csrc/pmg_internal.h)."""
+    return (SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP) if sweep_type == SOR_SYMMETRIC_SWEEP else (sweep_type,)
+
+
 class PMGError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"pmg status {code}: {msg}")

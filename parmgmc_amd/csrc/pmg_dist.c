@@ -454,35 +454,30 @@ static pmg_status ipc_sample(pmg_dist d, const double *b, double *y, int32_t its
     }
     PMG_KERNEL(pmgk_xch_push_dbg(&push, d->xch_counter, d->err_dev + 4, s));
   }
-  uint64_t ctr = counter0;
-  for (int32_t it = 0; it < its; ++it) {
-    const int ndir = sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-    for (int q = 0; q < ndir; ++q) {
-      const int dir = sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? (q == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : sweep_type;
-      for (int cc = 0; cc < 2; ++cc) {
-        const int      c = dir == PMG_SOR_FORWARD_SWEEP ? cc : 1 - cc;
-        pmgk_grid_halo h;
-        memset(&h, 0, sizeof h);
-        h.full = 1;
-        h.glo  = d->lo >= 0 ? d->recv + (int64_t)((1 - c) * 2 + 0) * d->plane : NULL;
-        h.ghi  = d->hi >= 0 ? d->recv + (int64_t)((1 - c) * 2 + 1) * d->plane : NULL;
-        h.plo  = d->lo >= 0 ? d->peer_recv[0] + (int64_t)(c * 2 + 1) * d->plane : NULL;
-        h.phi  = d->hi >= 0 ? d->peer_recv[1] + (int64_t)(c * 2 + 0) * d->plane : NULL;
-        h.wlo  = d->lo >= 0 ? flag_mine(d, (1 - c) * 2 + 0) : NULL; /* colour c reads colour 1-c across the slab faces */
-        h.whi  = d->hi >= 0 ? flag_mine(d, (1 - c) * 2 + 1) : NULL;
-        h.wval = d->round[1 - c];
-        d->round[c] += 1;
-        h.slo     = flag_peer(d, 0, c * 2 + 1);
-        h.shi     = flag_peer(d, 1, c * 2 + 0);
-        h.sval    = d->round[c];
-        h.counter = d->xch_counter + 1;
-        h.err     = d->err_dev;
-        h.spins   = d->spins_dev;
-        PMG_CALL(pmg_grid_sweep_color_halo_cvec(d->g, c, noisy, scaled, seed, ctr, &h, b, y, s));
-      }
-      if ((ctr & 1) == 1) PMG_CALL(ipc_throttle(d, s)); /* an event every other sweep: each one costs a marker on the stream */
-      ++ctr;
+  pmg_sweep_iter it = pmg_sweep_begin(sweep_type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    for (int cc = 0; cc < 2; ++cc) {
+      const int      c = pmg_sweep_color(it.dir, 2, cc);
+      pmgk_grid_halo h;
+      memset(&h, 0, sizeof h);
+      h.full = 1;
+      h.glo  = d->lo >= 0 ? d->recv + (int64_t)((1 - c) * 2 + 0) * d->plane : NULL;
+      h.ghi  = d->hi >= 0 ? d->recv + (int64_t)((1 - c) * 2 + 1) * d->plane : NULL;
+      h.plo  = d->lo >= 0 ? d->peer_recv[0] + (int64_t)(c * 2 + 1) * d->plane : NULL;
+      h.phi  = d->hi >= 0 ? d->peer_recv[1] + (int64_t)(c * 2 + 0) * d->plane : NULL;
+      h.wlo  = d->lo >= 0 ? flag_mine(d, (1 - c) * 2 + 0) : NULL; /* colour c reads colour 1-c across the slab faces */
+      h.whi  = d->hi >= 0 ? flag_mine(d, (1 - c) * 2 + 1) : NULL;
+      h.wval = d->round[1 - c];
+      d->round[c] += 1;
+      h.slo     = flag_peer(d, 0, c * 2 + 1);
+      h.shi     = flag_peer(d, 1, c * 2 + 0);
+      h.sval    = d->round[c];
+      h.counter = d->xch_counter + 1;
+      h.err     = d->err_dev;
+      h.spins   = d->spins_dev;
+      PMG_CALL(pmg_grid_sweep_color_halo_cvec(d->g, c, noisy, scaled, seed, it.sweep, &h, b, y, s));
     }
+    if ((it.sweep & 1) == 1) PMG_CALL(ipc_throttle(d, s)); /* an event every other sweep: each one costs a marker on the stream */
   }
   { /* leave y self-contained: the latest neighbour planes go into its own ghost planes, one launch */
     pmgk_xch_args pull;
@@ -499,7 +494,7 @@ static pmg_status ipc_sample(pmg_dist d, const double *b, double *y, int32_t its
       }
     PMG_KERNEL(pmgk_xch_pull(&pull, d->err_dev, s));
   }
-  if (counter_out) *counter_out = ctr;
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 
@@ -794,25 +789,19 @@ static pmg_status dist_sweeps(pmg_dist d, const double *b, double *y, int32_t it
   PMG_HIP(hipEventRecord(d->evS, s));
   PMG_CALL(dist_exchange(d, 0, y, d->evS));
   PMG_CALL(dist_exchange(d, 1, y, d->evS));
-  uint64_t ctr = counter0;
-  for (int32_t it = 0; it < its; ++it) {
-    const int ndir = sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-    for (int q = 0; q < ndir; ++q) {
-      const int dir = sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? (q == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : sweep_type;
-      for (int cc = 0; cc < 2; ++cc) {
-        const int c = dir == PMG_SOR_FORWARD_SWEEP ? cc : 1 - cc;
-        PMG_HIP(hipStreamWaitEvent(s, d->evX[1 - c], 0)); /* colour c reads colour 1-c across the slab faces */
-        PMG_CALL(pmg_grid_sweep_color_faces_cvec(d->g, c, noisy, scaled, seed, ctr, NULL, b, y, s)); /* planes 0 and nz-1, one launch */
-        PMG_HIP(hipEventRecord(d->evB[c], s));
-        PMG_CALL(dist_exchange(d, c, y, d->evB[c]));
-        if (nz > 2) PMG_CALL(pmg_grid_sweep_color_planes_cvec(d->g, c, 1, nz - 2, noisy, scaled, seed, ctr, b, y, s));
-      }
-      ++ctr;
+  pmg_sweep_iter it = pmg_sweep_begin(sweep_type, its, noisy, counter0);
+  while (pmg_sweep_next(&it))
+    for (int cc = 0; cc < 2; ++cc) {
+      const int c = pmg_sweep_color(it.dir, 2, cc);
+      PMG_HIP(hipStreamWaitEvent(s, d->evX[1 - c], 0)); /* colour c reads colour 1-c across the slab faces */
+      PMG_CALL(pmg_grid_sweep_color_faces_cvec(d->g, c, noisy, scaled, seed, it.sweep, NULL, b, y, s)); /* planes 0 and nz-1, one launch */
+      PMG_HIP(hipEventRecord(d->evB[c], s));
+      PMG_CALL(dist_exchange(d, c, y, d->evB[c]));
+      if (nz > 2) PMG_CALL(pmg_grid_sweep_color_planes_cvec(d->g, c, 1, nz - 2, noisy, scaled, seed, it.sweep, b, y, s));
     }
-  }
   PMG_HIP(hipStreamWaitEvent(s, d->evX[0], 0));
   PMG_HIP(hipStreamWaitEvent(s, d->evX[1], 0));
-  if (counter_out) *counter_out = ctr;
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 

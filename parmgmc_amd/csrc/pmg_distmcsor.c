@@ -197,34 +197,34 @@ static pmg_status distmcsor_refresh(pmg_distmcsor h, double *y, void *stream)
   return PMG_SUCCESS;
 }
 
-/* with_lrc = 0: the sweeps of A alone (what MCSORBuildLRCCorrection applies to the columns of B) */
+/* one direction over all colours, each colour's rows followed by its ghost update (a pmg_det_sweep_fn) */
+static pmg_status distmcsor_one_sweep(void *ctx, int dir, const double *rhs, double *y, void *stream)
+{
+  const pmg_sweep_args *a = (const pmg_sweep_args *)ctx;
+  pmg_distmcsor         h = (pmg_distmcsor)a->obj;
+  for (int32_t cc = 0; cc < h->ncolors; ++cc) {
+    const int32_t c = pmg_sweep_color(dir, h->ncolors, cc);
+    PMG_CALL(pmg_mcsor_sweep_color_layout(h->mc, c, a->noisy, a->scaled, a->seed, a->sweep, rhs, y, stream));
+    PMG_CALL(distmcsor_update(h, c, y, stream));
+  }
+  return PMG_SUCCESS;
+}
+
+/* with_lrc = 0: the sweeps of A alone (what MCSORBuildLRCCorrection applies to the columns of B).  The noise term's eta is keyed
+   on (seed, counter), the same on every rank.  The repair needs no exchange: B has zeros on the ghost rows (every row counts once
+   in the all-reduced k-vector), Bb carries the owners' values there, so the ghost rows receive their owners' update */
 static pmg_status distmcsor_sweeps_x(pmg_distmcsor h, const double *b, double *y, int32_t its, int noisy, int scaled, int sweep_type, uint64_t seed, uint64_t counter0, uint64_t *counter_out, int with_lrc, void *stream)
 {
   PMG_CHECK(h && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
   PMG_CHECK(pmg_sweep_type_ok(sweep_type), PMG_ERR_SUP, "Only forward, backward and symmetric sweep supported");
-  pmg_lrc lrc = with_lrc ? h->lrc : NULL;
   PMG_CALL(distmcsor_refresh(h, y, stream)); /* the caller's y has no ghost values yet */
-  uint64_t ctr = counter0;
-  for (int32_t it = 0; it < its; ++it) {
-    const int ndir = sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-    for (int q = 0; q < ndir; ++q) {
-      const int     dir = ndir == 2 ? (q == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : sweep_type;
-      const double *rhs = b;
-      if (lrc && noisy) PMG_CALL(pmg_lrc_rhs(lrc, b, seed, ctr, &rhs, stream)); /* + B (sqrt(S) o eta), src/pc_mcgibbs.c:130-140: eta is keyed on (seed, counter), the same on every rank */
-      for (int32_t cc = 0; cc < h->ncolors; ++cc) {
-        const int32_t c = dir == PMG_SOR_FORWARD_SWEEP ? cc : h->ncolors - 1 - cc; /* src/mc_sor.c:317, :344 */
-        PMG_CALL(pmg_mcsor_sweep_color_layout(h->mc, c, noisy, scaled, seed, ctr, rhs, y, stream));
-        PMG_CALL(distmcsor_update(h, c, y, stream));
-      }
-      if (lrc && noisy) PMG_CALL(pmg_lrc_rhs_done(lrc, stream));
-      /* y -= Bb (B^T y), src/mc_sor.c:101-112: B has zeros on the ghost rows (every row counts once in the all-reduced
-         k-vector), Bb carries the owners' values there, so the ghost rows receive their owners' update without an exchange */
-      if (lrc) PMG_CALL(pmg_lrc_post(lrc, dir, y, stream));
-      ++ctr; /* a symmetric sweep draws twice per sample, src/pc_mcgibbs.c:172-181 */
-    }
+  pmg_sweep_iter it = pmg_sweep_begin(sweep_type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    pmg_sweep_args a = {h, noisy, scaled, seed, it.sweep};
+    PMG_CALL(pmg_lrc_dir_sweep(with_lrc ? h->lrc : NULL, noisy, it.dir, seed, it.sweep, distmcsor_one_sweep, &a, b, &y, stream));
   }
-  if (counter_out) *counter_out = ctr;
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 

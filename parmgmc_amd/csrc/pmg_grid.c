@@ -187,32 +187,48 @@ static void pmg_grid_fill_op(pmg_grid g, pmgk_grid_op *op, int noisy, int scaled
   op->omega_is_one = g->omega == 1.0;
 }
 
-/* One forward (colours 0,1) or backward (colours 1,0; src/mc_sor.c:274) sweep, with the low-rank noise term and
-   repair (src/pc_mcgibbs.c:130-140, src/mc_sor.c:101-112) when a MATLRC update is attached. */
-static pmg_status pmg_grid_one_sweep(pmg_grid g, int dir, int noisy, int scaled, uint64_t seed, uint64_t sweep, const double *b, double *y, void *stream)
+/* both colours of one directional sweep, in its order */
+static int grid_color_launches(pmg_grid g, const pmgk_grid_op *op, int dir, const double *b, double *y, void *stream)
 {
-  if (g->lrc && noisy) PMG_CALL(pmg_lrc_rhs(g->lrc, b, seed, sweep, &b, stream));
-  pmgk_grid_op op;
-  pmg_grid_fill_op(g, &op, noisy, scaled, seed, sweep);
-  const int c0 = dir == PMG_SOR_FORWARD_SWEEP ? 0 : 1;
+  int rc = 0;
+  for (int cc = 0; cc < 2 && !rc; ++cc) rc = pmgk_grid_color_sweep(&g->L, op, pmg_sweep_color(dir, 2, cc), 0, g->L.nz, 1, NULL, b, y, stream);
+  return rc;
+}
+
+/* one directional sweep of a sample or an apply (a pmg_det_sweep_fn) */
+static pmg_status grid_one_sweep(void *ctx, int dir, const double *b, double *y, void *stream)
+{
+  const pmg_sweep_args *a = (const pmg_sweep_args *)ctx;
+  pmg_grid              g = (pmg_grid)a->obj;
+  pmgk_grid_op          op;
+  pmg_grid_fill_op(g, &op, a->noisy, a->scaled, a->seed, a->sweep);
   pmg_trace_begin(PMG_EVENT_MULTICOL_SOR); /* PetscLogEventBegin(MULTICOL_SOR), src/mc_sor.c:221 */
-  int rc = pmgk_grid_color_sweep(&g->L, &op, c0, 0, g->L.nz, 1, NULL, b, y, stream);
-  if (!rc) rc = pmgk_grid_color_sweep(&g->L, &op, 1 - c0, 0, g->L.nz, 1, NULL, b, y, stream);
+  const int rc = grid_color_launches(g, &op, dir, b, y, stream);
   pmg_trace_end();
   PMG_KERNEL(rc);
-  if (g->lrc && noisy) PMG_CALL(pmg_lrc_rhs_done(g->lrc, stream));
-  if (g->lrc) PMG_CALL(pmg_lrc_post(g->lrc, dir, y, stream));
   return PMG_SUCCESS;
 }
 
+/* the deterministic sweep the low-rank correction is built with (no trace range) */
 static pmg_status grid_det_sweep(void *ctx, int dir, const double *b, double *y, void *stream)
 {
   pmg_grid     g = (pmg_grid)ctx;
   pmgk_grid_op op;
   pmg_grid_fill_op(g, &op, 0, 0, 0, 0);
-  const int c0 = dir == PMG_SOR_FORWARD_SWEEP ? 0 : 1;
-  PMG_KERNEL(pmgk_grid_color_sweep(&g->L, &op, c0, 0, g->L.nz, 1, NULL, b, y, stream));
-  PMG_KERNEL(pmgk_grid_color_sweep(&g->L, &op, 1 - c0, 0, g->L.nz, 1, NULL, b, y, stream));
+  const int rc = grid_color_launches(g, &op, dir, b, y, stream);
+  PMG_KERNEL(rc);
+  return PMG_SUCCESS;
+}
+
+/* `its` samples of the object's sweep type on cvec vectors, each directional sweep with the low-rank bracket */
+static pmg_status grid_sweeps(pmg_grid g, int32_t its, int noisy, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, const double *b, double *y, void *stream)
+{
+  pmg_sweep_iter it = pmg_sweep_begin(g->type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    pmg_sweep_args a = {g, noisy, scaled, seed, it.sweep};
+    PMG_CALL(pmg_lrc_dir_sweep(g->lrc, noisy, it.dir, seed, it.sweep, grid_one_sweep, &a, b, &y, stream));
+  }
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 
@@ -248,7 +264,7 @@ pmg_status pmg_grid_sweep_color_cvec(pmg_grid g, int color, int noisy, int scale
 {
   PMG_CHECK(g && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(color == 0 || color == 1, PMG_ERR_ARG_OUTOFRANGE, "colour %d", color);
-  PMG_CHECK(!noisy || scaled || g->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(noisy, scaled, g->omega);
   pmgk_grid_op op;
   pmg_grid_fill_op(g, &op, noisy != 0, scaled, seed, counter);
   PMG_KERNEL(pmgk_grid_color_sweep(&g->L, &op, color, 0, g->L.nz, 1, NULL, b, y, stream));
@@ -260,7 +276,7 @@ pmg_status pmg_grid_sweep_color_planes_cvec(pmg_grid g, int color, int32_t kbegi
   PMG_CHECK(g && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(color == 0 || color == 1, PMG_ERR_ARG_OUTOFRANGE, "colour %d", color);
   PMG_CHECK(kbegin >= 0 && kcount >= 0 && kbegin + kcount <= g->L.nz, PMG_ERR_ARG_OUTOFRANGE, "planes [%d,%d) outside the %d owned planes", kbegin, kbegin + kcount, g->L.nz);
-  PMG_CHECK(!noisy || scaled || g->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(noisy, scaled, g->omega);
   pmgk_grid_op op;
   pmg_grid_fill_op(g, &op, noisy != 0, scaled, seed, counter);
   PMG_KERNEL(pmgk_grid_color_sweep(&g->L, &op, color, kbegin, kcount, 1, NULL, b, y, stream));
@@ -272,7 +288,7 @@ pmg_status pmg_grid_sweep_color_faces_cvec(pmg_grid g, int color, int noisy, int
 {
   PMG_CHECK(g && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(color == 0 || color == 1, PMG_ERR_ARG_OUTOFRANGE, "colour %d", color);
-  PMG_CHECK(!noisy || scaled || g->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(noisy, scaled, g->omega);
   pmgk_grid_op op;
   pmg_grid_fill_op(g, &op, noisy != 0, scaled, seed, counter);
   const int nz = g->L.nz;
@@ -286,7 +302,7 @@ pmg_status pmg_grid_sweep_color_halo_cvec(pmg_grid g, int color, int noisy, int 
 {
   PMG_CHECK(g && b && y && halo && halo->full, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(color == 0 || color == 1, PMG_ERR_ARG_OUTOFRANGE, "colour %d", color);
-  PMG_CHECK(!noisy || scaled || g->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(noisy, scaled, g->omega);
   pmgk_grid_op op;
   pmg_grid_fill_op(g, &op, noisy != 0, scaled, seed, counter);
   PMG_KERNEL(pmgk_grid_color_sweep(&g->L, &op, color, 0, g->L.nz, 1, halo, b, y, stream));
@@ -307,31 +323,15 @@ pmg_status pmg_grid_halo_plane(pmg_grid g, int color, int side, int64_t *owned_o
 pmg_status pmg_grid_apply_cvec(pmg_grid g, const double *b, double *y, void *stream)
 {
   PMG_CHECK(g && b && y, PMG_ERR_ARG_NULL, "null argument");
-  if (g->type == PMG_SOR_SYMMETRIC_SWEEP) { /* src/mc_sor.c:223-232 */
-    PMG_CALL(pmg_grid_one_sweep(g, PMG_SOR_FORWARD_SWEEP, 0, 0, 0, 0, b, y, stream));
-    PMG_CALL(pmg_grid_one_sweep(g, PMG_SOR_BACKWARD_SWEEP, 0, 0, 0, 0, b, y, stream));
-  } else {
-    PMG_CALL(pmg_grid_one_sweep(g, g->type, 0, 0, 0, 0, b, y, stream));
-  }
-  return PMG_SUCCESS;
+  return grid_sweeps(g, 1, 0, 0, 0, 0, NULL, b, y, stream);
 }
 
 pmg_status pmg_grid_sample_cvec(pmg_grid g, const double *b, double *y, int32_t its, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, void *stream)
 {
   PMG_CHECK(g && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
-  PMG_CHECK(scaled || g->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
-  uint64_t ctr = counter0;
-  for (int it = 0; it < its; ++it) {
-    if (g->type == PMG_SOR_SYMMETRIC_SWEEP) { /* two sweeps, two fresh draws: src/pc_mcgibbs.c:172-181 */
-      PMG_CALL(pmg_grid_one_sweep(g, PMG_SOR_FORWARD_SWEEP, 1, scaled, seed, ctr++, b, y, stream));
-      PMG_CALL(pmg_grid_one_sweep(g, PMG_SOR_BACKWARD_SWEEP, 1, scaled, seed, ctr++, b, y, stream));
-    } else {
-      PMG_CALL(pmg_grid_one_sweep(g, g->type, 1, scaled, seed, ctr++, b, y, stream));
-    }
-  }
-  if (counter_out) *counter_out = ctr;
-  return PMG_SUCCESS;
+  PMG_CHECK_UNSCALED_NOISE(1, scaled, g->omega);
+  return grid_sweeps(g, its, 1, scaled, seed, counter0, counter_out, b, y, stream);
 }
 
 pmg_status pmg_grid_residual_cvec(pmg_grid g, const double *b, const double *y, double *r, void *stream)

@@ -38,6 +38,45 @@ pmg_status pmg_set_error(pmg_status code, const char *file, int line, const char
 
 static inline int pmg_sweep_type_ok(int t) { return t == PMG_SOR_FORWARD_SWEEP || t == PMG_SOR_BACKWARD_SWEEP || t == PMG_SOR_SYMMETRIC_SWEEP; }
 
+/* ---- the sweep schedule of every sampler: "`its` samples of sweep type `type`, starting at draw counter counter0" ----
+   A symmetric sample is a forward, then a backward directional sweep (src/mc_sor.c:223-232).  Every noisy directional
+   sweep takes the next draw counter, so a symmetric sample draws twice (src/pc_mcgibbs.c:172-181).  A forward sweep visits
+   the colours in ascending, a backward one in descending order (src/mc_sor.c:256-289, :317, :344).
+     pmg_sweep_iter it = pmg_sweep_begin(type, its, noisy, counter0);
+     while (pmg_sweep_next(&it)) ... one directional sweep it.dir with draw counter it.sweep ...
+     if (counter_out) *counter_out = it.ctr; */
+typedef struct {
+  int      type, noisy;
+  int64_t  total, index; /* directional sweeps of the call; the current one's number, from 0 */
+  uint64_t counter0;
+  int      dir;   /* PMG_SOR_FORWARD_SWEEP or PMG_SOR_BACKWARD_SWEEP */
+  uint64_t sweep; /* counter0 + index: the draw counter of a noisy sweep (a deterministic sweep reads none) */
+  uint64_t ctr;   /* what the call hands back through counter_out: behind the last noisy sweep so far */
+} pmg_sweep_iter;
+
+static inline int pmg_sweep_ndir(int type) { return type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1; }
+
+static inline pmg_sweep_iter pmg_sweep_begin(int type, int32_t its, int noisy, uint64_t counter0)
+{
+  const pmg_sweep_iter it = {type, noisy, (int64_t)its * pmg_sweep_ndir(type), -1, counter0, type, counter0, counter0};
+  return it;
+}
+
+static inline int pmg_sweep_next(pmg_sweep_iter *it) /* 0 at the end */
+{
+  if (it->index + 1 >= it->total) return 0;
+  ++it->index;
+  it->dir   = it->type != PMG_SOR_SYMMETRIC_SWEEP ? it->type : (it->index % 2 == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP);
+  it->sweep = it->counter0 + (uint64_t)it->index;
+  if (it->noisy) it->ctr = it->sweep + 1;
+  return 1;
+}
+
+/* the cc-th colour a directional sweep visits */
+static inline int32_t pmg_sweep_color(int dir, int32_t ncolors, int32_t cc) { return dir == PMG_SOR_FORWARD_SWEEP ? cc : ncolors - 1 - cc; }
+
+#define PMG_CHECK_UNSCALED_NOISE(noisy, scaled, omega) PMG_CHECK(!(noisy) || (scaled) || (omega) == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)")
+
 pmg_status pmg_grid_set_lowrank_dev(pmg_grid g, int32_t k, const double *B_cvec_dev, const double *S_host);
 pmg_status pmg_grid_sweep_color_halo_cvec(pmg_grid g, int color, int noisy, int scaled, uint64_t seed, uint64_t counter, const pmgk_grid_halo *halo, const double *b, double *y, void *stream);
 pmg_status pmg_grid_sweep_color_faces_cvec(pmg_grid g, int color, int noisy, int scaled, uint64_t seed, uint64_t counter, const pmgk_grid_halo *halo, const double *b, double *y, void *stream);
@@ -52,12 +91,22 @@ pmg_status pmg_grid_residual_restrict(pmg_grid g, const double *b, const double 
 /* low-rank (MATLRC) helper shared by pmg_mcsor and pmg_grid (pmg_lrc.c); vectors in the sampler's layout */
 typedef struct pmg_lrc_s *pmg_lrc;
 typedef pmg_status (*pmg_det_sweep_fn)(void *ctx, int dir, const double *b_lay, double *y_lay, void *stream);
+/* what a sampler's directional sweep needs besides (dir, b, y): the usual context of a pmg_det_sweep_fn */
+typedef struct {
+  void    *obj; /* the sampler */
+  int      noisy, scaled;
+  uint64_t seed, sweep;
+} pmg_sweep_args;
 typedef pmg_status (*pmg_lrc_reduce_fn)(void *ctx, double *vals_dev, int count, void *stream);
 pmg_status pmg_lrc_build_dev(pmg_lrc *out, int32_t k, int64_t ld, const double *B_lay_dev, const double *S_host, pmg_det_sweep_fn det, void *ctx, pmg_lrc_reduce_fn reduce, void *rctx);
 pmg_status pmg_lrc_build(pmg_lrc *out, int32_t k, int64_t ld, int32_t n, const double *B_nat_host, const int64_t *pos, const double *S_host, pmg_det_sweep_fn det, void *ctx);
 pmg_status pmg_lrc_rhs(pmg_lrc l, const double *b_lay, uint64_t seed, uint64_t counter, const double **beff, void *stream);
 pmg_status pmg_lrc_rhs_done(pmg_lrc l, void *stream); /* after the sweep that used the vector pmg_lrc_rhs returned */
 pmg_status pmg_lrc_post(pmg_lrc l, int dir, double *y_lay, void *stream);
+/* one directional sweep of an operator with an optional update (l = NULL: the sweep alone).  The sweep itself is sweep_fn(ctx, dir, rhs,
+   *y_lay, stream): ctx->sor(...) then ctx->postsor(...) of src/mc_sor.c:223-236, with the extra noise term of PrepareRHS_LRC
+   (src/pc_mcgibbs.c:130-140) on rhs when the sweep is a noisy one.  *y_lay is read again behind the sweep, which may swap the iterate's buffers */
+pmg_status pmg_lrc_dir_sweep(pmg_lrc l, int noisy, int dir, uint64_t seed, uint64_t counter, pmg_det_sweep_fn sweep_fn, void *ctx, const double *b_lay, double *const *y_lay, void *stream);
 pmg_status pmg_lrc_residual_sub(pmg_lrc l, const double *x_lay, double *r_lay, void *stream);
 pmg_status pmg_lrc_residual_sub_restricted(pmg_lrc l_fine, pmg_lrc l_coarse, const double *x_fine_lay, double *b_coarse_lay, void *stream);
 void       pmg_lrc_preset_eta(pmg_lrc l, uint64_t seed, uint64_t counter0, int n, const double *eta_dev, int64_t stride); /* noise terms drawn ahead */

@@ -498,6 +498,17 @@ pmg_status pmg_lrc_post(pmg_lrc l, int dir, double *y_lay, void *stream)
   return PMG_SUCCESS;
 }
 
+/* the bracket every sampler puts around a directional sweep: noise term, sweep, restore, repair */
+pmg_status pmg_lrc_dir_sweep(pmg_lrc l, int noisy, int dir, uint64_t seed, uint64_t counter, pmg_det_sweep_fn sweep_fn, void *ctx, const double *b_lay, double *const *y_lay, void *stream)
+{
+  const double *rhs = b_lay;
+  if (l && noisy) PMG_CALL(pmg_lrc_rhs(l, b_lay, seed, counter, &rhs, stream));
+  PMG_CALL(sweep_fn(ctx, dir, rhs, *y_lay, stream));
+  if (l && noisy) PMG_CALL(pmg_lrc_rhs_done(l, stream));
+  if (l) PMG_CALL(pmg_lrc_post(l, dir, *y_lay, stream));
+  return PMG_SUCCESS;
+}
+
 /* ---- many chains of one operator (pmg_mcsor_sample_chains / pmg_mcsor_apply_chains): Y and the right-hand sides are ld x C
    doubles in the layout, chain fastest.  Column c performs the single-chain calls' arithmetic (kernels_lrc_chains.hip): the
    noise term of pmg_lrc_rhs with the key pmg_lrc_noise_seed(keys[c]) and the repair of pmg_lrc_post, in both storage forms. */

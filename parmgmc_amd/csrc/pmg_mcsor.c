@@ -533,32 +533,40 @@ pmg_status pmg_mcsor_get_coloring(pmg_mcsor mc, int32_t *colors)
   return PMG_SUCCESS;
 }
 
-/* one direction over all colours on permuted vectors (src/mc_sor.c:256-289: colours ascending / descending) */
-static pmg_status mcsor_one_sweep(pmg_mcsor mc, int dir, int noisy, int scaled, uint64_t seed, uint64_t sweep, const double *b_p, double *y_p, void *stream)
+/* mc->S with the noise scaling of the call */
+static pmgk_sell mcsor_sell(pmg_mcsor mc, int scaled)
 {
   pmgk_sell S = mc->S;
   S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
-  int rc      = 0;
+  return S;
+}
+
+/* one direction over all colours on layout vectors (a pmg_det_sweep_fn) */
+static pmg_status mcsor_one_sweep(void *ctx, int dir, const double *b_p, double *y_p, void *stream)
+{
+  const pmg_sweep_args *a  = (const pmg_sweep_args *)ctx;
+  pmg_mcsor             mc = (pmg_mcsor)a->obj;
+  const pmgk_sell       S  = mcsor_sell(mc, a->scaled);
+  int                   rc = 0;
   pmg_trace_begin(PMG_EVENT_MULTICOL_SOR); /* PetscLogEventBegin(MULTICOL_SOR), src/mc_sor.c:221 */
-  if (dir == PMG_SOR_FORWARD_SWEEP) {
-    for (int32_t c = 0; c < mc->ncolors && !rc; ++c) rc = pmgk_sell_color_sweep(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, seed, sweep, b_p, y_p, stream);
-  } else {
-    for (int32_t c = mc->ncolors - 1; c >= 0 && !rc; --c) rc = pmgk_sell_color_sweep(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, seed, sweep, b_p, y_p, stream);
+  for (int32_t cc = 0; cc < mc->ncolors && !rc; ++cc) {
+    const int32_t c = pmg_sweep_color(dir, mc->ncolors, cc);
+    rc = pmgk_sell_color_sweep(&S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, a->noisy, a->seed, a->sweep, b_p, y_p, stream);
   }
   pmg_trace_end();
   PMG_KERNEL(rc);
   return PMG_SUCCESS;
 }
 
-/* one directional sweep + the low-rank repair: ctx->sor(...) then ctx->postsor(...) of src/mc_sor.c:223-236, with
-   the extra noise term of PrepareRHS_LRC (src/pc_mcgibbs.c:130-140) when the sweep is a noisy one */
-static pmg_status mcsor_sweep_lrc(pmg_mcsor mc, int dir, int noisy, int scaled, uint64_t seed, uint64_t sweep, const double *b_p, double *y_p, void *stream)
+/* `its` samples of the object's sweep type on layout vectors, each directional sweep with the low-rank bracket */
+static pmg_status mcsor_sweeps(pmg_mcsor mc, int32_t its, int noisy, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, const double *b_lay, double *y_lay, void *stream)
 {
-  const double *rhs = b_p;
-  if (mc->lrc && noisy) PMG_CALL(pmg_lrc_rhs(mc->lrc, b_p, seed, sweep, &rhs, stream));
-  PMG_CALL(mcsor_one_sweep(mc, dir, noisy, scaled, seed, sweep, rhs, y_p, stream));
-  if (mc->lrc && noisy) PMG_CALL(pmg_lrc_rhs_done(mc->lrc, stream));
-  if (mc->lrc) PMG_CALL(pmg_lrc_post(mc->lrc, dir, y_p, stream));
+  pmg_sweep_iter it = pmg_sweep_begin(mc->type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    pmg_sweep_args a = {mc, noisy, scaled, seed, it.sweep};
+    PMG_CALL(pmg_lrc_dir_sweep(mc->lrc, noisy, it.dir, seed, it.sweep, mcsor_one_sweep, &a, b_lay, &y_lay, stream));
+  }
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 
@@ -575,12 +583,7 @@ pmg_status pmg_mcsor_apply(pmg_mcsor mc, const double *b, double *y, void *strea
   PMG_CALL(mcsor_ready(mc));
   PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->b_p, stream));
   PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, y, mc->y_p, stream));
-  if (mc->type == PMG_SOR_SYMMETRIC_SWEEP) { /* src/mc_sor.c:223-232 */
-    PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_FORWARD_SWEEP, 0, 0, 0, 0, mc->b_p, mc->y_p, stream));
-    PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_BACKWARD_SWEEP, 0, 0, 0, 0, mc->b_p, mc->y_p, stream));
-  } else {
-    PMG_CALL(mcsor_sweep_lrc(mc, mc->type, 0, 0, 0, 0, mc->b_p, mc->y_p, stream));
-  }
+  PMG_CALL(pmg_mcsor_apply_layout(mc, mc->b_p, mc->y_p, stream));
   PMG_KERNEL(pmgk_permute_out(mc->S.ld, mc->S.orig, mc->y_p, y, stream));
   return PMG_SUCCESS;
 }
@@ -589,21 +592,12 @@ pmg_status pmg_mcsor_sample(pmg_mcsor mc, const double *b, double *y, int32_t it
 {
   PMG_CHECK(mc && b && y, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
-  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(1, scaled, mc->omega);
   PMG_CALL(mcsor_ready(mc));
   PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b, mc->b_p, stream));
   PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, y, mc->y_p, stream));
-  uint64_t ctr = counter0;
-  for (int it = 0; it < its; ++it) {
-    if (mc->type == PMG_SOR_SYMMETRIC_SWEEP) { /* src/pc_mcgibbs.c:172-181 */
-      PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_FORWARD_SWEEP, 1, scaled, seed, ctr++, mc->b_p, mc->y_p, stream));
-      PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_BACKWARD_SWEEP, 1, scaled, seed, ctr++, mc->b_p, mc->y_p, stream));
-    } else {
-      PMG_CALL(mcsor_sweep_lrc(mc, mc->type, 1, scaled, seed, ctr++, mc->b_p, mc->y_p, stream));
-    }
-  }
+  PMG_CALL(pmg_mcsor_sample_layout(mc, mc->b_p, mc->y_p, its, scaled, seed, counter0, counter_out, stream));
   PMG_KERNEL(pmgk_permute_out(mc->S.ld, mc->S.orig, mc->y_p, y, stream));
-  if (counter_out) *counter_out = ctr;
   return PMG_SUCCESS;
 }
 
@@ -624,9 +618,8 @@ pmg_status pmg_mcsor_sweep_color_layout(pmg_mcsor mc, int32_t color, int noisy, 
   PMG_CALL(mcsor_ready(mc));
   PMG_CHECK(color >= 0 && color < mc->ncolors, PMG_ERR_ARG_OUTOFRANGE, "colour %d of %d", color, mc->ncolors);
   PMG_CHECK(!mc->lrc, PMG_ERR_SUP, "per-colour sweeps do not carry the low-rank repair");
-  PMG_CHECK(!noisy || scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
-  pmgk_sell S = mc->S;
-  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
+  PMG_CHECK_UNSCALED_NOISE(noisy, scaled, mc->omega);
+  const pmgk_sell S = mcsor_sell(mc, scaled);
   PMG_KERNEL(pmgk_sell_color_sweep(&S, mc->cslice[color], mc->cslice[color + 1] - mc->cslice[color], mc->omega, noisy, seed, sweep, b_lay, y_lay, stream));
   return PMG_SUCCESS;
 }
@@ -690,32 +683,16 @@ pmg_status pmg_mcsor_apply_layout(pmg_mcsor mc, const double *b_lay, double *y_l
 {
   PMG_CHECK(mc && b_lay && y_lay, PMG_ERR_ARG_NULL, "null argument");
   PMG_CALL(mcsor_ready(mc));
-  if (mc->type == PMG_SOR_SYMMETRIC_SWEEP) {
-    PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_FORWARD_SWEEP, 0, 0, 0, 0, b_lay, y_lay, stream));
-    PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_BACKWARD_SWEEP, 0, 0, 0, 0, b_lay, y_lay, stream));
-  } else {
-    PMG_CALL(mcsor_sweep_lrc(mc, mc->type, 0, 0, 0, 0, b_lay, y_lay, stream));
-  }
-  return PMG_SUCCESS;
+  return mcsor_sweeps(mc, 1, 0, 0, 0, 0, NULL, b_lay, y_lay, stream);
 }
 
 pmg_status pmg_mcsor_sample_layout(pmg_mcsor mc, const double *b_lay, double *y_lay, int32_t its, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, void *stream)
 {
   PMG_CHECK(mc && b_lay && y_lay, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
-  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(1, scaled, mc->omega);
   PMG_CALL(mcsor_ready(mc));
-  uint64_t ctr = counter0;
-  for (int it = 0; it < its; ++it) {
-    if (mc->type == PMG_SOR_SYMMETRIC_SWEEP) {
-      PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_FORWARD_SWEEP, 1, scaled, seed, ctr++, b_lay, y_lay, stream));
-      PMG_CALL(mcsor_sweep_lrc(mc, PMG_SOR_BACKWARD_SWEEP, 1, scaled, seed, ctr++, b_lay, y_lay, stream));
-    } else {
-      PMG_CALL(mcsor_sweep_lrc(mc, mc->type, 1, scaled, seed, ctr++, b_lay, y_lay, stream));
-    }
-  }
-  if (counter_out) *counter_out = ctr;
-  return PMG_SUCCESS;
+  return mcsor_sweeps(mc, its, 1, scaled, seed, counter0, counter_out, b_lay, y_lay, stream);
 }
 
 pmg_status pmg_mcsor_residual_layout(pmg_mcsor mc, const double *b_lay, const double *y_lay, double *r_lay, void *stream)
@@ -725,11 +702,6 @@ pmg_status pmg_mcsor_residual_layout(pmg_mcsor mc, const double *b_lay, const do
   PMG_KERNEL(pmgk_sell_residual(&mc->S, b_lay, y_lay, r_lay, stream));
   if (mc->lrc) PMG_CALL(pmg_lrc_residual_sub(mc->lrc, y_lay, r_lay, stream));
   return PMG_SUCCESS;
-}
-
-static pmg_status mcsor_det_sweep(void *ctx, int dir, const double *b_lay, double *y_lay, void *stream)
-{
-  return mcsor_one_sweep((pmg_mcsor)ctx, dir, 0, 0, 0, 0, b_lay, y_lay, stream);
 }
 
 /* MCSORSetUp's MATLRC branch (src/mc_sor.c:572-595): B is n x k column-major in the matrix's row numbering,
@@ -744,7 +716,8 @@ pmg_status pmg_mcsor_set_lowrank(pmg_mcsor mc, int32_t k, const double *B_host, 
   PMG_CHECK(pos, PMG_ERR_MEM, "out of host memory");
   for (int32_t p = 0; p < mc->S.ld; ++p)
     if (mc->orig_host[p] >= 0) pos[mc->orig_host[p]] = p;
-  pmg_status st = pmg_lrc_build(&mc->lrc, k, mc->S.ld, mc->n, B_host, pos, S_host, mcsor_det_sweep, mc);
+  pmg_sweep_args det = {mc, 0, 0, 0, 0}; /* the deterministic sweep */
+  pmg_status     st  = pmg_lrc_build(&mc->lrc, k, mc->S.ld, mc->n, B_host, pos, S_host, mcsor_one_sweep, &det);
   free(pos);
   return st;
 }
@@ -798,81 +771,56 @@ pmg_lrc pmg_mcsor_lrc(pmg_mcsor mc) { return mc ? mc->lrc : NULL; }
 
 const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc) { return mc->S.orig; }
 
-/* `its` times the directional sweeps of the sweep type (symmetric = forward + backward), every directional sweep with the next
-   counter when noisy: pmg_mcsor_sample_layout / pmg_mcsor_apply_layout on C chains */
 /* one directional sweep over all colours on C chains */
 static pmg_status mcsor_dir_chains(pmg_mcsor mc, const pmgk_sell *S, int dir, int32_t nchains, const uint64_t *keys_dev, int noisy, uint64_t sweep, const double *b_lay, int bcs, double *Y_lay, void *stream)
 {
   int rc = 0;
   pmg_trace_begin(PMG_EVENT_MULTICOL_SOR);
-  if (dir == PMG_SOR_FORWARD_SWEEP) {
-    for (int32_t c = 0; c < mc->ncolors && !rc; ++c) rc = pmgk_sell_color_sweep_chains(S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
-  } else {
-    for (int32_t c = mc->ncolors - 1; c >= 0 && !rc; --c) rc = pmgk_sell_color_sweep_chains(S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
+  for (int32_t cc = 0; cc < mc->ncolors && !rc; ++cc) {
+    const int32_t c = pmg_sweep_color(dir, mc->ncolors, cc);
+    rc = pmgk_sell_color_sweep_chains(S, mc->cslice[c], mc->cslice[c + 1] - mc->cslice[c], mc->omega, noisy, keys_dev, sweep, nchains, b_lay, bcs, Y_lay, stream);
   }
   pmg_trace_end();
   PMG_KERNEL(rc);
   return PMG_SUCCESS;
 }
 
+/* mcsor_sweeps on C chains, every directional sweep as pmg_lrc_dir_sweep per column.  With a low-rank update lrc (else NULL) a noisy
+   sweep runs on rhs_lay (ld x C), whose support rows get b + B (sqrt(S) o eta_c) first (the caller has filled the other rows with
+   b); then the repair y -= Bb (B^T y) */
+static pmg_status mcsor_sweeps_chains(pmg_mcsor mc, pmg_lrc lrc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *rhs_lay, double *Y_lay, void *stream)
+{
+  PMG_CALL(mcsor_ready(mc));
+  const pmgk_sell S    = mcsor_sell(mc, scaled);
+  const int       term = lrc && noisy;
+  pmg_sweep_iter  it   = pmg_sweep_begin(mc->type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    if (term) PMG_CALL(pmg_lrc_rhs_chains(lrc, nchains, keys_dev, it.sweep, b_lay, bcs, rhs_lay, stream));
+    PMG_CALL(mcsor_dir_chains(mc, &S, it.dir, nchains, keys_dev, noisy, it.sweep, term ? rhs_lay : b_lay, term ? 1 : bcs, Y_lay, stream));
+    if (lrc) PMG_CALL(pmg_lrc_post_chains(lrc, nchains, it.dir, Y_lay, stream));
+  }
+  if (counter_out) *counter_out = it.ctr;
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_mcsor_sweeps_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *Y_lay, void *stream)
 {
-  PMG_CALL(mcsor_ready(mc));
-  pmgk_sell S = mc->S;
-  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
-  uint64_t ctr = counter0;
-  for (int32_t it = 0; it < its; ++it) {
-    const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-    for (int d = 0; d < ndir; ++d) {
-      const int      dir   = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
-      const uint64_t sweep = noisy ? ctr++ : 0;
-      PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, noisy, sweep, b_lay, bcs, Y_lay, stream));
-    }
-  }
-  if (counter_out) *counter_out = ctr;
-  return PMG_SUCCESS;
+  return mcsor_sweeps_chains(mc, NULL, nchains, keys_dev, noisy, scaled, its, counter0, counter_out, b_lay, bcs, NULL, Y_lay, stream);
 }
 
-/* pmg_mcsor_sweeps_chains on an operator with a low-rank update, every directional sweep as mcsor_sweep_lrc per column: a noisy
-   sweep runs on rhs_lay (ld x C), whose support rows get b + B (sqrt(S) o eta_c) first (the caller has filled the other rows
-   with b); then the repair y -= Bb (B^T y) */
-static pmg_status mcsor_sweeps_lrc_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int noisy, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *b_lay, int bcs, double *rhs_lay, double *Y_lay, void *stream)
-{
-  PMG_CALL(mcsor_ready(mc));
-  pmgk_sell S = mc->S;
-  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
-  uint64_t ctr = counter0;
-  for (int32_t it = 0; it < its; ++it) {
-    const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-    for (int d = 0; d < ndir; ++d) {
-      const int      dir   = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
-      const uint64_t sweep = noisy ? ctr++ : 0;
-      if (noisy) PMG_CALL(pmg_lrc_rhs_chains(mc->lrc, nchains, keys_dev, sweep, b_lay, bcs, rhs_lay, stream));
-      PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, noisy, sweep, noisy ? rhs_lay : b_lay, noisy ? 1 : bcs, Y_lay, stream));
-      PMG_CALL(pmg_lrc_post_chains(mc->lrc, nchains, dir, Y_lay, stream));
-    }
-  }
-  if (counter_out) *counter_out = ctr;
-  return PMG_SUCCESS;
-}
-
-/* the sweeps of the chains V-cycle on such an operator: per directional sweep the noise term in place (one launch), the colour
-   sweeps, the repair with the restore (one launch on a small support, else three) */
+/* the sweeps of the chains V-cycle on an operator with a low-rank update: per directional sweep the noise term in place (one
+   launch), the colour sweeps, the repair with the restore (one launch on a small support, else three) */
 pmg_status pmg_mcsor_sweeps_lowrank_chains(pmg_mcsor mc, int32_t nchains, const uint64_t *keys_dev, int scaled, int32_t its, uint64_t counter0, uint64_t *counter_out, const double *eta_dev, int64_t eta_stride, double *B_lay, double *Y_lay, void *stream)
 {
   PMG_CALL(mcsor_ready(mc));
-  pmgk_sell S = mc->S;
-  S.sqrtdiag  = scaled ? mc->sqrtd_scaled_dev : mc->sqrtd_dev;
-  uint64_t  ctr  = counter0;
-  const int ndir = mc->type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-  for (int32_t i = 0; i < its * ndir; ++i) {
-    const int      dir   = ndir == 2 ? (i % 2 == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : mc->type;
-    const uint64_t sweep = ctr++;
-    PMG_CALL(pmg_lrc_rhs_inplace_chains(mc->lrc, nchains, eta_dev + (int64_t)i * eta_stride, B_lay, stream));
-    PMG_CALL(mcsor_dir_chains(mc, &S, dir, nchains, keys_dev, 1, sweep, B_lay, 1, Y_lay, stream));
-    PMG_CALL(pmg_lrc_post_restore_chains(mc->lrc, nchains, dir, Y_lay, stream));
+  const pmgk_sell S  = mcsor_sell(mc, scaled);
+  pmg_sweep_iter  it = pmg_sweep_begin(mc->type, its, 1, counter0);
+  while (pmg_sweep_next(&it)) {
+    PMG_CALL(pmg_lrc_rhs_inplace_chains(mc->lrc, nchains, eta_dev + it.index * eta_stride, B_lay, stream));
+    PMG_CALL(mcsor_dir_chains(mc, &S, it.dir, nchains, keys_dev, 1, it.sweep, B_lay, 1, Y_lay, stream));
+    PMG_CALL(pmg_lrc_post_restore_chains(mc->lrc, nchains, it.dir, Y_lay, stream));
   }
-  if (counter_out) *counter_out = ctr;
+  if (counter_out) *counter_out = it.ctr;
   return PMG_SUCCESS;
 }
 
@@ -936,14 +884,11 @@ static pmg_status mcsor_chains_run(pmg_mcsor mc, int32_t nchains, const uint64_t
   } else PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b_nat, mc->ch_b, stream));
   PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
   const uint64_t *keys = noisy ? mc->ch_keys.dev : NULL;
-  if (!mc->lrc) PMG_CALL(pmg_mcsor_sweeps_chains(mc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_Y, stream));
-  else {
-    if (noisy) { /* the noisy sweeps' right-hand sides: b everywhere, the support rows rewritten before every sweep */
-      PMG_CALL(mcsor_chains_buf(mc, &mc->ch_bc, &mc->ch_bc_cap, nchains, stream));
-      PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, bcs, mc->ch_bc, stream));
-    }
-    PMG_CALL(mcsor_sweeps_lrc_chains(mc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_bc, mc->ch_Y, stream));
+  if (mc->lrc && noisy) { /* the noisy sweeps' right-hand sides: b everywhere, the support rows rewritten before every sweep */
+    PMG_CALL(mcsor_chains_buf(mc, &mc->ch_bc, &mc->ch_bc_cap, nchains, stream));
+    PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, bcs, mc->ch_bc, stream));
   }
+  PMG_CALL(mcsor_sweeps_chains(mc, mc->lrc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_bc, mc->ch_Y, stream));
   PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
   return PMG_SUCCESS;
 }
@@ -960,7 +905,7 @@ pmg_status pmg_mcsor_sample_chains(pmg_mcsor mc, int32_t nchains, const uint64_t
 {
   PMG_CALL(mcsor_chains_args(mc, nchains, 1, seeds, b, Y));
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
-  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(1, scaled, mc->omega);
   return mcsor_chains_run(mc, nchains, seeds, 1, b, 0, Y, its, scaled, counter0, counter_out, stream);
 }
 
@@ -969,7 +914,7 @@ pmg_status pmg_mcsor_sample_chains_rhs(pmg_mcsor mc, int32_t nchains, const uint
 {
   PMG_CALL(mcsor_chains_args(mc, nchains, 1, seeds, B, Y));
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
-  PMG_CHECK(scaled || mc->omega == 1.0, PMG_ERR_SUP, "the unscaled (sorgibbs) noise requires omega = 1 (src/pc_sorgibbs.c:94)");
+  PMG_CHECK_UNSCALED_NOISE(1, scaled, mc->omega);
   return mcsor_chains_run(mc, nchains, seeds, 1, B, 1, Y, its, scaled, counter0, counter_out, stream);
 }
 

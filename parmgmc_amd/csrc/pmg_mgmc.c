@@ -119,20 +119,29 @@ pmg_status pmg_mgmc_i_halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stre
    level of a z-slab hierarchy): noise term, directional sweep (the part that differs), repair, halo */
 typedef pmg_status (*mg_dir_sweep)(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream);
 
+typedef struct {
+  pmg_mgmc     h;
+  mg_level    *Lv;
+  mg_dir_sweep sweep;
+  uint64_t     seed, *ctr;
+} mg_sweep_args;
+
+/* the level's directional sweep as a pmg_det_sweep_fn: it sweeps the level's own iterate and advances the level's counter */
+static pmg_status mg_one_sweep(void *ctx, int dir, const double *rhs, double *x, void *stream)
+{
+  const mg_sweep_args *a = (const mg_sweep_args *)ctx;
+  (void)x;
+  return a->sweep(a->h, a->Lv, dir, rhs, a->seed, a->ctr, stream);
+}
+
 static pmg_status mg_lowrank_sweeps(pmg_mgmc h, mg_level *Lv, int its, mg_dir_sweep sweep, uint64_t seed, uint64_t *ctr, void *stream)
 {
-  const int ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-  for (int it = 0; it < its; ++it)
-    for (int d = 0; d < ndir; ++d) {
-      const int     dir = ndir == 2 ? (d == 0 ? PMG_SOR_FORWARD_SWEEP : PMG_SOR_BACKWARD_SWEEP) : h->sweep_type;
-      const double *rhs = Lv->b;
-      if (Lv->lrc) PMG_CALL(pmg_lrc_rhs(Lv->lrc, Lv->b, seed, *ctr, &rhs, stream)); /* + B (sqrt(S) o eta), src/pc_mcgibbs.c:130-140 */
-      PMG_CALL(sweep(h, Lv, dir, rhs, seed, ctr, stream));
-      if (!Lv->lrc) continue;
-      PMG_CALL(pmg_lrc_rhs_done(Lv->lrc, stream));
-      PMG_CALL(pmg_lrc_post(Lv->lrc, dir, Lv->x, stream)); /* src/mc_sor.c:101-112 */
-      PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, Lv->x, stream));          /* the repair changed boundary planes */
-    }
+  mg_sweep_args  a  = {h, Lv, sweep, seed, ctr};
+  pmg_sweep_iter it = pmg_sweep_begin(h->sweep_type, its, 1, *ctr);
+  while (pmg_sweep_next(&it)) {
+    PMG_CALL(pmg_lrc_dir_sweep(Lv->lrc, 1, it.dir, seed, *ctr, mg_one_sweep, &a, Lv->b, &Lv->x, stream)); /* an out-of-place sweep swaps Lv->x */
+    if (Lv->lrc) PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, Lv->x, stream)); /* the repair changed boundary planes */
+  }
   return PMG_SUCCESS;
 }
 
@@ -310,7 +319,7 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
     h->eta_batch_mode = (e && !atoi(e)) ? -1 : 1;
   }
   const int env = h->eta_batch_mode > 0;
-  const int top = h->nlevels - 1, ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
+  const int top = h->nlevels - 1;
   uint64_t  seeds[PMGK_NORMAL_BATCH_MAX], ctrs[PMGK_NORMAL_BATCH_MAX];
   int       first[64], count[64], nslots = 0;
   pmg_lrc   any = NULL;
@@ -321,7 +330,7 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
     if (!lr) continue;
     pmg_lrc_preset_eta(lr, 0, 0, 0, NULL, 0); /* forget the last cycle's */
     if (!on || !env || h->dist || !pmg_lrc_is_local(lr) || pmg_lrc_rank(lr) > MG_ETA_STRIDE) continue;
-    const int n = l >= 1 ? 2 * h->nu * ndir : (h->coarse_type != 0 ? h->coarse_its * ndir : 0); /* pre- and post-smoothing; the sampled coarsest level */
+    const int n = pmg_mgmc_i_level_sweeps(h, l);
     if (n <= 0 || nslots + n > PMGK_NORMAL_BATCH_MAX) continue;
     first[l] = nslots;
     count[l] = n;
@@ -468,8 +477,6 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
   PMG_CHECK(h && total, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(h->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_mgmc_setup first");
   const int    top  = h->nlevels - 1;
-  const int    ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-  const double nsw  = (double)h->nu * ndir; /* directional sweeps per smoothing leg */
   *total            = 0.0;
   for (int l = 0; l <= top; ++l) {
     const mg_level *Lv = &h->lv[l];
@@ -486,11 +493,11 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
     const double lrres = p.lrc ? (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns : 0.0; /* unrestricted residual term */
     double       by    = p.zero_guess == MG_GUESS_FILL ? 8.0 * N : (p.zero_guess == MG_GUESS_UNSET ? -8.0 * N : 0.0); /* the zero fill / the first sweep does not read x */
     if (l == 0) {
-      by += h->coarse_type == 0 ? 8.0 * N * N : h->coarse_its * ndir * (sweep + lrsw);
+      by += h->coarse_type == 0 ? 8.0 * N * N : pmg_mgmc_i_level_sweeps(h, l) * (sweep + lrsw);
     } else {
       const mg_level *Cc = &h->lv[l - 1];
       const double    Nc = level_rows(Cc);
-      by += 2.0 * nsw * (sweep + lrsw);
+      by += pmg_mgmc_i_level_sweeps(h, l) * (sweep + lrsw);
       if (p.rr != MG_RR_TWO) by += 16.0 * N + 8.0 * Nc;
       else if (Lv->is_grid || Lv->is_st27) by += 24.0 * N + 8.0 * N + 8.0 * Nc;
       else by += 12.0 * (double)Lv->A_nnz + 28.0 * N + 12.0 * (double)Lv->P_nnz + 12.0 * Nc + 8.0 * N;

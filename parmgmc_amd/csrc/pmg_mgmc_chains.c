@@ -13,13 +13,6 @@
    whose factor is that of the explicit sum */
 static pmg_lrc chains_lrc(const struct pmg_mgmc_s *h, int l) { return h->lv[l].mc && !(l == 0 && h->coarse_type == 0) ? pmg_mcsor_lrc(h->lv[l].mc) : NULL; }
 
-/* directional sweeps of one cycle on level l */
-static int chains_level_sweeps(const struct pmg_mgmc_s *h, int l)
-{
-  const int ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-  return l >= 1 ? 2 * h->nu * ndir : (h->coarse_type != 0 ? h->coarse_its * ndir : 0);
-}
-
 void pmg_mgmc_i_free_chains(pmg_mgmc h)
 {
   for (int l = 0; l < h->nlevels && h->ch_b; ++l) {
@@ -83,7 +76,7 @@ static pmg_status chains_draw_lowrank_noise(pmg_mgmc h, int32_t C, const uint64_
   plan.n = 0;
   for (int l = 0; l < h->nlevels; ++l) {
     pmg_lrc   lr = chains_lrc(h, l);
-    const int n  = chains_level_sweeps(h, l);
+    const int n  = pmg_mgmc_i_level_sweeps(h, l);
     first[l]     = nslots;
     if (!lr || n <= 0) continue;
     plan.level[plan.n] = l;
@@ -108,7 +101,7 @@ static pmg_status chains_draw_lowrank_noise(pmg_mgmc h, int32_t C, const uint64_
   return PMG_SUCCESS;
 }
 
-/* `its` samples of level l's sampler from draw number *done of the cycle on: plain sweeps on (b, bcs), or, on a level with a
+/* one smoothing leg (`its` samples) of level l's sampler from draw number *done of the cycle on: plain sweeps on (b, bcs), or, on a level with a
    low-rank update, on bown -- the same right-hand side as ld x C doubles the cycle may write (the noise term goes in and out) */
 static pmg_status chains_smooth(pmg_mgmc h, int l, int32_t C, const uint64_t *keys, int its, uint64_t *ctr, int first, int *done, const double *b, int bcs, double *bown, double *x, void *stream)
 {
@@ -117,7 +110,7 @@ static pmg_status chains_smooth(pmg_mgmc h, int l, int32_t C, const uint64_t *ke
   if (!lr) return pmg_mcsor_sweeps_chains(Lv->mc, C, keys + (size_t)l * C, 1, h->scaled, its, *ctr, ctr, b, bcs, x, stream);
   const int64_t kc = (int64_t)pmg_lrc_rank(lr) * C;
   PMG_CALL(pmg_mcsor_sweeps_lowrank_chains(Lv->mc, C, keys + (size_t)l * C, h->scaled, its, *ctr, ctr, h->ch_eta + (int64_t)(first + *done) * kc, kc, bown, x, stream));
-  *done += its * (h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1);
+  *done += pmg_mgmc_i_leg_sweeps(h, l);
   return PMG_SUCCESS;
 }
 
@@ -291,7 +284,7 @@ static double chains_lowrank_bytes(pmg_mgmc h, int l, double Cd)
   int       dense;
   pmg_lrc_get_sizes(lr, &k, &ns, &dense);
   const double K = k, N = (double)h->lv[l].n, n = dense ? N : (double)ns, idx = dense ? 0.0 : 8.0 * n;
-  const double nb = dense ? (double)((h->lv[l].n + 4095) / 4096) : (double)((ns + 1023) / 1024), s = chains_level_sweeps(h, l);
+  const double nb = dense ? (double)((h->lv[l].n + 4095) / 4096) : (double)((ns + 1023) / 1024), s = pmg_mgmc_i_level_sweeps(h, l);
   const double noise = 8.0 * K * n + idx + 8.0 * K * Cd + 24.0 * n * Cd, upd = 8.0 * K * n + idx + 8.0 * K * Cd + 16.0 * n * Cd;
   const double btx = 8.0 * K * n + idx + 8.0 * n * Cd + 8.0 * nb * K * Cd, red = 8.0 * nb * K * Cd + 8.0 * K * Cd, one = 16.0 * K * n + idx + 24.0 * n * Cd;
   const int    fused  = pmg_lrc_chains_fused(lr);
@@ -299,7 +292,7 @@ static double chains_lowrank_bytes(pmg_mgmc h, int l, double Cd)
   const double resid  = fused ? one + 8.0 * K : btx + red + 8.0 * K + upd;
   double       by     = s * (noise + repair) + 8.0 * K * Cd * s + 8.0 * Cd;
   if (l >= 1) by += resid;
-  if (l == top) by += 8.0 * K + (h->correction_form ? resid : 2.0 * h->nu * (h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1) * (8.0 * N * Cd - 8.0 * N));
+  if (l == top) by += 8.0 * K + (h->correction_form ? resid : 2.0 * h->nu * pmg_sweep_ndir(h->sweep_type) * (8.0 * N * Cd - 8.0 * N));
   return by;
 }
 
@@ -309,19 +302,18 @@ pmg_status pmg_mgmc_get_algorithmic_bytes_chains(pmg_mgmc h, int32_t C, double *
   PMG_CHECK(C >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", C);
   PMG_CALL(mgmc_chains_check(h, C));
   const int    top  = h->nlevels - 1;
-  const int    ndir = h->sweep_type == PMG_SOR_SYMMETRIC_SWEEP ? 2 : 1;
-  const double nsw  = (double)h->nu * ndir, Cd = (double)C;
+  const double Cd   = (double)C;
   *total            = 0.0;
   for (int l = 0; l <= top; ++l) {
     const mg_level *Lv  = &h->lv[l];
     const double    N   = (double)Lv->n, nnz = (double)Lv->A_nnz;
     const double    swp = 12.0 * nnz + 16.0 * N + 24.0 * N * Cd; /* per-chain b */
     double          by  = 0.0;
-    if (l == 0) by = h->coarse_type == 0 ? 8.0 * N * N + 48.0 * N * Cd : 8.0 * N * Cd + h->coarse_its * ndir * swp;
+    if (l == 0) by = h->coarse_type == 0 ? 8.0 * N * N + 48.0 * N * Cd : 8.0 * N * Cd + pmg_mgmc_i_level_sweeps(h, l) * swp;
     else {
       const double Nc     = (double)h->lv[l - 1].n, nnzP = (double)Lv->P_nnz;
       const int    shared = l == top && !h->correction_form;
-      by += 2.0 * nsw * (shared ? 12.0 * nnz + 24.0 * N + 16.0 * N * Cd : swp);
+      by += pmg_mgmc_i_level_sweeps(h, l) * (shared ? 12.0 * nnz + 24.0 * N + 16.0 * N * Cd : swp);
       if (!shared) by += 8.0 * N * Cd;                                                   /* zero fill */
       by += 12.0 * nnz + 12.0 * N + 16.0 * N * Cd + (shared ? 8.0 * N : 8.0 * N * Cd); /* residual */
       by += 12.0 * nnzP + 8.0 * Nc + 8.0 * N * Cd + 8.0 * Nc * Cd;                     /* restriction */

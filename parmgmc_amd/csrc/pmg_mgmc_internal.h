@@ -130,6 +130,12 @@ static inline void hcsr_move(hcsr *to, hcsr *from)
 /* per-level noise seed: levels draw from independent streams */
 static inline uint64_t level_seed(uint64_t seed, int level) { return seed + 0x9E3779B97F4A7C15ull * (uint64_t)(level + 1); }
 
+/* directional sweeps of ONE smoothing leg of level l (nu samples; coarse_its on a Gibbs coarsest level, none on an exactly sampled
+   one), and of one whole cycle (pre- and post-smoothing above the coarsest level).  The batched noise draws of a cycle and the
+   sweeps that later ask for them count with these two, as do the byte models */
+static inline int pmg_mgmc_i_leg_sweeps(const struct pmg_mgmc_s *h, int l) { return (l >= 1 ? h->nu : (h->coarse_type != 0 ? h->coarse_its : 0)) * pmg_sweep_ndir(h->sweep_type); }
+static inline int pmg_mgmc_i_level_sweeps(const struct pmg_mgmc_s *h, int l) { return (l >= 1 ? 2 : 1) * pmg_mgmc_i_leg_sweeps(h, l); }
+
 static inline double level_rows(const mg_level *Lv) { /* owned unknowns: a z-slab's planes, a row block's rows */ return Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n); }
 
 static inline pmgk_st27_dims level_dims(const mg_level *Lv) { return (pmgk_st27_dims){Lv->nx, Lv->ny, Lv->nzl, Lv->kz0, Lv->nz}; }

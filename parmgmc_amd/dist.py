@@ -15,7 +15,7 @@ torch is plumbing here: the sweeps are the HIP kernels behind the C-ABI.
 """
 from __future__ import annotations
 
-from .capi import SOR_BACKWARD_SWEEP, SOR_FORWARD_SWEEP, SOR_SYMMETRIC_SWEEP
+from .capi import SOR_FORWARD_SWEEP, directions
 from .slab import slab_cuts
 
 
@@ -66,11 +66,9 @@ class SlabHalo:
 
 
 def color_schedule(sweep_type: int):
-    """Order of (direction, colours) of one sample: forward = colours 0,1; backward = 1,0 (reference
-    src/mc_sor.c:257,274); symmetric = forward then backward with a fresh draw each (src/pc_mcgibbs.c:172-181)."""
-    if sweep_type == SOR_SYMMETRIC_SWEEP:
-        return [(0, 1), (1, 0)]
-    return [(0, 1)] if sweep_type == SOR_FORWARD_SWEEP else [(1, 0)]
+    """Colour order of every directional sweep of one sample (capi.directions): forward = colours 0,1; backward = 1,0
+    (reference src/mc_sor.c:257,274)."""
+    return [(0, 1) if d == SOR_FORWARD_SWEEP else (1, 0) for d in directions(sweep_type)]
 
 
 def run_samples(sweep_planes, halo: SlabHalo, nz: int, b, y, its: int, sweep_type: int, counter0: int) -> int:
@@ -641,7 +639,7 @@ class DistMCSOR:
             self.exchange(y, c)
         ctr = counter0
         for _ in range(its):
-            for direction in ((SOR_FORWARD_SWEEP, SOR_BACKWARD_SWEEP) if self.sweep_type == SOR_SYMMETRIC_SWEEP else (self.sweep_type,)):
+            for direction in directions(self.sweep_type):
                 order = range(self.ncolors) if direction == SOR_FORWARD_SWEEP else range(self.ncolors - 1, -1, -1)
                 for c in order:
                     self.mc.sweep_color_layout(c, b, y, True, self.scaled, seed, ctr)

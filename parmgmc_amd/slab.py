@@ -8,7 +8,7 @@ from __future__ import annotations
 
 import numpy as np
 
-from .capi import SOR_BACKWARD_SWEEP, SOR_FORWARD_SWEEP, SOR_SYMMETRIC_SWEEP
+from .capi import SOR_FORWARD_SWEEP, directions
 from .wrappers import GridMCSOR
 
 
@@ -60,11 +60,7 @@ class SlabSet:
             ys.append(s.to_cvec(torch.as_tensor(np.ascontiguousarray(y0[lo * plane:hi * plane]), device="cuda")))
         ctr = counter0
         for _ in range(its):
-            if self.type == SOR_SYMMETRIC_SWEEP:
-                self.one_sweep(bs, ys, SOR_FORWARD_SWEEP, True, scaled, seed, ctr)
-                self.one_sweep(bs, ys, SOR_BACKWARD_SWEEP, True, scaled, seed, ctr + 1)
-                ctr += 2
-            else:
-                self.one_sweep(bs, ys, self.type, True, scaled, seed, ctr)
+            for direction in directions(self.type):
+                self.one_sweep(bs, ys, direction, True, scaled, seed, ctr)
                 ctr += 1
         return np.concatenate([s.from_cvec(y).cpu().numpy() for s, y in zip(self.slabs, ys)])
