@@ -14,7 +14,7 @@
 // -ffp-contract=off (no FMA contraction), like the CPU oracle.
 #include <hip/hip_runtime.h>
 #include <cstring>
-#include <stdlib.h>
+#include "pmg_switch.h"
 #include "pmg_kernels.h"
 #define PMG_RNG_TU grid
 #include "pmg_rng.hpp"
@@ -913,20 +913,11 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 static inline int grid_threads_per_line(const pmgk_grid_layout *L) { return ((L->nx + 1) / 2 + 1) / 2; }
 static inline bool grid_use_packed(const pmgk_grid_layout *L)
 {
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("PMG_GRID_PACKED");
-    env           = e ? atoi(e) : 2; // 0 = never, 1 = always, 2 = by lane efficiency
-  }
+  const int env = pmg_switch(PMG_SW_GRID_PACKED); // 0 = never, 1 = always, 2 = by lane efficiency
   if (env != 2) return env == 1;
   const int tplE = grid_threads_per_line(L), lanes = (L->sx / 2 + 63) / 64 * 64;
   return 2 * lanes >= 3 * tplE;
 }
-
-// 0: one plane per wavefront everywhere (grid_color_sweep_kernel), as before the plane-pair kernel.  Held to the default's
-// bits, and to INTEGRATION.md section 5, by tests/test_gpu_grid_plane_pair.py rather than by the tables of
-// tests/test_runtime_switch_inventory.py, which find a switch by the literal in its getenv call.
-static const char *const grid_plane_pair_key = "PMG_GRID_PLANE_PAIR";
 
 // how one plane's threads are dealt to the wavefronts
 struct grid_mapping {
@@ -938,17 +929,8 @@ struct grid_mapping {
 static grid_mapping grid_choose_mapping(const pmgk_grid_layout *L, int kcount, bool allow_tail, bool allow_flat = false, bool allow_pair = false)
 {
   const int kcount_planes = kcount;
-  static int banded_env = -1, tail_env = -1, flat_env = -1, pair_env = -1;
-  if (banded_env < 0) {
-    const char *e = getenv("PMG_GRID_BANDED");
-    banded_env    = e ? atoi(e) : 1;
-    e             = getenv("PMG_GRID_TAIL");
-    tail_env      = e ? atoi(e) : 1;
-    e             = getenv("PMG_GRID_FLAT");
-    flat_env      = e ? atoi(e) : 1;
-    e             = getenv(grid_plane_pair_key);
-    pair_env      = e ? atoi(e) : 1;
-  }
+  // PMG_GRID_PLANE_PAIR=0: one plane per wavefront everywhere (grid_color_sweep_kernel), as before the plane-pair kernel
+  const int banded_env = pmg_switch(PMG_SW_GRID_BANDED), tail_env = pmg_switch(PMG_SW_GRID_TAIL), flat_env = pmg_switch(PMG_SW_GRID_FLAT), pair_env = pmg_switch(PMG_SW_GRID_PLANE_PAIR);
   grid_mapping M;
   const int    tpl = L->sx / 2, tplE = grid_threads_per_line(L);
   M.nby   = (L->ny + 3) / 4;
@@ -1080,7 +1062,7 @@ extern "C" int pmgk_grid_residual(const pmgk_grid_layout *L, const pmgk_grid_op 
 // hierarchy evaluates it on every rank and agrees on the result before any rank relies on it
 extern "C" int pmgk_grid_residual_restrict_applies(const pmgk_grid_layout *L, const pmgk_st27_dims *C, int have_lo2, int have_hi2)
 {
-  static const int off  = getenv("PMG_GRID_FUSED_RR") ? !atoi(getenv("PMG_GRID_FUSED_RR")) : 0;
+  const int        off  = !pmg_switch(PMG_SW_GRID_FUSED_RR);
   const int        tplE = grid_threads_per_line(L);
   const bool       slab = L->kz0 != 0 || L->nz != L->nzg;
   if (off || C->nz <= 0) return 0;
@@ -1096,13 +1078,13 @@ extern "C" int pmgk_grid_residual_restrict_applies(const pmgk_grid_layout *L, co
 
 extern "C" int pmgk_grid_residual_restrict(const pmgk_grid_layout *L, const pmgk_grid_op *op, const pmgk_st27_dims *C, const double *b, const double *y, const double *ylo2, const double *yhi2, double *bc, void *stream)
 {
-  static const int kc_env = getenv("PMG_GRID_RR_CHUNK") ? atoi(getenv("PMG_GRID_RR_CHUNK")) : 0;
+  const int kc_env = pmg_switch(PMG_SW_GRID_RR_CHUNK);
   if (!pmgk_grid_residual_restrict_applies(L, C, ylo2 != nullptr, yhi2 != nullptr)) return -1;
   const int     tplE = grid_threads_per_line(L);
   // one barrier per plane step (see the kernel): -3 % time and fabric reads at 513^3 and 257^3, +5 % on grids of a few
   // microseconds, where the wavefronts barely drift (tools/rrbench.py, tools/pmc_one.sh; PMG_GRID_RR_SYNC = 0 | 1 forces)
-  static const int sync_knob = getenv("PMG_GRID_RR_SYNC") ? atoi(getenv("PMG_GRID_RR_SYNC")) : -1;
-  const int        sync_env  = sync_knob >= 0 ? sync_knob : ((int64_t)L->nx * L->ny * L->nz >= 8000000);
+  const int     sync_knob = pmg_switch(PMG_SW_GRID_RR_SYNC);
+  const int     sync_env  = sync_knob >= 0 ? sync_knob : ((int64_t)L->nx * L->ny * L->nz >= 8000000);
   const int     wpp = (int)(((int64_t)C->ny * tplE + 61) / 62);
   int           kc  = kc_env > 0 ? kc_env : 8; // coarse planes per chunk: each chunk re-reads one fine plane
   while (kc_env <= 0 && kc > 2 && (int64_t)wpp * ((C->nz + kc - 1) / kc) < 2048) kc >>= 1;

@@ -16,7 +16,7 @@
 // neighbours contributing an exact +0, and the noise is the row stream of the natural index, so results are
 // bit-identical to the sliced-ELL kernel on the assembled matrix.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
+#include "pmg_switch.h"
 #include "pmg_kernels.h"
 #define PMG_RNG_LITERALS // the transform's constants as literals here: scalar loads in the middle of these kernels' sums cost more than they save (st27 phase +9 % by GRBM_GUI_ACTIVE)
 #define PMG_RNG_TU st27
@@ -291,8 +291,7 @@ __global__ __launch_bounds__(256) void st27_prolong_add_cell_kernel(pmgk_st27_di
 
 inline bool st27_transfer_full_case(const pmgk_st27_dims *F, const pmgk_st27_dims *C)
 {
-  static const int off = getenv("PMG_TRANSFER_GENERIC") != nullptr;
-  if (off || F->nx == C->nx || F->ny == C->ny || F->nzg == C->nzg) return false;
+  if (pmg_switch(PMG_SW_TRANSFER_GENERIC) || F->nx == C->nx || F->ny == C->ny || F->nzg == C->nzg) return false;
   return (int64_t)F->nx * F->ny * (F->nz + 2) * 8 < ((int64_t)1 << 31);
 }
 
@@ -309,11 +308,7 @@ extern "C" int pmgk_st27_sweep_phase(const pmgk_st27 *S, int backward, int phase
   // one workgroup per plane pays only while the launch latency of four kernels is what a phase costs: measured on
   // MI355X, planes of 33 x 33 points gain (257^3 V-cycle 0.912 -> 0.893 ms), 65 x 65 break even, 129 x 129 and larger
   // lose (one CU per plane is latency-bound: 1.05 ms)
-  static int plane_limit = -1;
-  if (plane_limit < 0) {
-    const char *e = getenv("PMG_ST27_PHASE_MAX_PLANE");
-    plane_limit   = e ? atoi(e) : 1100; /* points per plane up to which the plane kernel is used */
-  }
+  const int plane_limit = pmg_switch(PMG_SW_ST27_PHASE_MAX_PLANE); /* points per plane up to which the plane kernel is used */
   if ((int64_t)S->nx * S->ny <= plane_limit) {
     const int pz = backward ? 1 - phase : phase;
     const int kfirst = S->kz0 + ((pz - S->kz0) & 1), cz = (S->kz0 + S->nz - kfirst + 1) / 2;

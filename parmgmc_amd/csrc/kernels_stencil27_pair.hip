@@ -27,7 +27,7 @@
 // ones entering with a zero table coefficient at a valid address), the file is compiled with -ffp-contract=off, so
 // results are bit-identical to the per-colour kernel and to the sliced-ELL sweep of the assembled matrix.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
+#include "pmg_switch.h"
 #include "pmg_kernels.h"
 #define PMG_RNG_LITERALS // the transform's constants as literals here: scalar loads in the middle of these kernels' sums cost more than they save (st27 phase +9 % by GRBM_GUI_ACTIVE)
 #define PMG_RNG_TU st27pair
@@ -115,11 +115,7 @@ static inline pair_split split_pairs(int npairs, int valid, int halo)
 {
   pair_split P;
   const int  nbx = (npairs + valid - 1) / valid, rem = npairs - valid * (nbx - 1), segw = rem + 2 * halo;
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("PMG_ST27_PACK_REMAINDER");
-    env           = e ? atoi(e) : 1;
-  }
+  const int  env = pmg_switch(PMG_SW_ST27_PACK_REMAINDER);
   if (env && 64 / segw >= 2) { // two or more remainders fit one wavefront
     P.nbx_main = nbx - 1;
     P.p0       = valid * (nbx - 1);

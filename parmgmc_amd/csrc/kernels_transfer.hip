@@ -9,7 +9,7 @@
 // Sums run over the same entries in the same (ascending fine / coarse index) order as the CSR product of the
 // stored transposed / plain interpolation, so results are bit-identical to the assembled operators.
 #include <hip/hip_runtime.h>
-#include <stdlib.h>
+#include "pmg_switch.h"
 #include "pmg_kernels.h"
 
 namespace {
@@ -256,8 +256,7 @@ inline int launch_status() { return hipGetLastError() == hipSuccess ? 0 : 1; }
 // all directions refined, natural coarse storage, and both vectors addressable with 32-bit byte offsets
 inline bool transfer_full_case(const pmgk_grid_layout *L, const pmgk_st27_dims *C, const int32_t *cpos)
 {
-  static const int off = getenv("PMG_TRANSFER_GENERIC") != nullptr;
-  if (off || cpos) return false;
+  if (pmg_switch(PMG_SW_TRANSFER_GENERIC) || cpos) return false;
   if (C->nx == L->nx || C->ny == L->ny || C->nzg == L->nzg) return false;
   if (2 * (int64_t)L->cs * 8 >= ((int64_t)1 << 31)) return false;
   return (int64_t)C->nx * C->ny * (C->nz + 2) * 8 < ((int64_t)1 << 31);

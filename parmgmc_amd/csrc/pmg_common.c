@@ -142,9 +142,9 @@ static pthread_once_t    pmg_trace_once = PTHREAD_ONCE_INIT;
 static void pmg_trace_probe(void)
 {
   static const char *names[] = {"librocprofiler-sdk-roctx.so.1", "librocprofiler-sdk-roctx.so", "libroctx64.so.4", "libroctx64.so"};
-  const char        *env     = getenv("PMG_TRACE");
-  const int          force   = env && env[0] == '1';
-  if (env && env[0] == '0') return;
+  const int          env     = pmg_switch(PMG_SW_TRACE);
+  const int          force   = env == '1';
+  if (env == '0') return;
   for (unsigned q = 0; q < sizeof names / sizeof names[0]; ++q) {
     void *h = dlopen(names[q], RTLD_LAZY | (force ? 0 : RTLD_NOLOAD));
     if (!h) continue;

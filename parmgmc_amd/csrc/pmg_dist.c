@@ -417,7 +417,7 @@ static uint64_t *flag_peer(pmg_dist d, int side, int idx) { return (side == 0 ? 
 static pmg_status ipc_check(pmg_dist d)
 {
   volatile unsigned *e = (volatile unsigned *)d->err_dev;
-  if (e[0] != 0 && getenv("PMG_IPC_DEBUG")) { /* my flag words as they are now: [0..3] colour planes, [4..5] generic, [8+r] all-gather */
+  if (e[0] != 0 && pmg_switch(PMG_SW_IPC_DEBUG)) { /* my flag words as they are now: [0..3] colour planes, [4..5] generic, [8+r] all-gather */
     uint64_t w[16];
     if (hipMemcpy(w, d->block, sizeof w, hipMemcpyDeviceToHost) == hipSuccess)
       fprintf(stderr, "[pmg ipc debug] rank %d block %p flags: planes %llu %llu %llu %llu generic %llu %llu gather %llu %llu %llu %llu; rounds %llu %llu ground %llu\n", d->rank, (void *)d->block, (unsigned long long)w[0], (unsigned long long)w[1], (unsigned long long)w[2], (unsigned long long)w[3], (unsigned long long)w[4], (unsigned long long)w[5], (unsigned long long)w[8], (unsigned long long)w[9], (unsigned long long)w[10], (unsigned long long)w[11], (unsigned long long)d->round[0], (unsigned long long)d->round[1], (unsigned long long)d->ground);

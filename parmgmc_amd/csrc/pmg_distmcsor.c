@@ -183,9 +183,7 @@ static pmg_status distmcsor_update(pmg_distmcsor h, int32_t c, double *y, void *
 static pmg_status distmcsor_refresh(pmg_distmcsor h, double *y, void *stream)
 {
   if (h->nranks == 1) return PMG_SUCCESS;
-  static int by_colour = -1; /* PMG_DISTMCSOR_REFRESH_BY_COLOUR=1: the colour-by-colour form (same values) */
-  if (by_colour < 0) by_colour = getenv("PMG_DISTMCSOR_REFRESH_BY_COLOUR") != NULL;
-  if (h->all_tot < 0 || by_colour) {
+  if (h->all_tot < 0 || pmg_switch(PMG_SW_DISTMCSOR_REFRESH_BY_COLOUR)) { /* PMG_DISTMCSOR_REFRESH_BY_COLOUR=1: the colour-by-colour form (same values) */
     for (int32_t c = 0; c < h->ncolors; ++c) PMG_CALL(distmcsor_update(h, c, y, stream));
     return PMG_SUCCESS;
   }

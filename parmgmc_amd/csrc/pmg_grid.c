@@ -44,8 +44,8 @@ static void pmg_grid_update_tables(pmg_grid g)
 int32_t pmg_grid_line_stride(int32_t nx, int32_t ny, int32_t nzg)
 {
   const int32_t half = (nx + 1) / 2;
-  const char   *e    = getenv("PMG_GRID_SX_ALIGN");
-  int32_t       al   = e ? atoi(e) : (16.0 * nx * ny * nzg <= 1.02 * 268435456.0 ? 2 : 16);
+  int32_t       al;
+  if (!pmg_switch_if_set(PMG_SW_GRID_SX_ALIGN, &al)) al = 16.0 * nx * ny * nzg <= 1.02 * 268435456.0 ? 2 : 16;
   if (al < 2 || (al & 1)) al = 16;
   return (half + al - 1) / al * al;
 }

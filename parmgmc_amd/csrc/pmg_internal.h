@@ -8,6 +8,7 @@
 #include <string.h>
 #include "../../include/parmgmc_hip.h"
 #include "pmg_kernels.h"
+#include "pmg_switch.h"
 
 #define PMG_VERSION_STRING "0.1.0"
 

@@ -203,16 +203,13 @@ pmg_status pmg_lrc_build_dev(pmg_lrc *out, int32_t k, int64_t ld, const double *
   l->reduce = reduce;
   l->rctx   = rctx;
   {
-    const char *e = getenv("PMG_LRC_FUSED"); /* 1: both fusions; 2: the noise term only; 3: the restore only */
-    l->unfused         = !(e && e[0] == '1');
-    l->unfused_rhs     = !(e && (e[0] == '1' || e[0] == '2'));
-    l->unfused_restore = !(e && (e[0] == '1' || e[0] == '3'));
-    const char *er     = getenv("PMG_LRC_RESTORE");
-    l->restore_in_btx  = l->unfused_restore && !(er && er[0] == '0');
-    const char *ed     = getenv("PMG_LRC_REDUCE");
-    l->reduce_in_axpy  = !(ed && ed[0] == '0');
-    const char *eb     = getenv("PMG_LRC_BTY");
-    l->bty_in_post     = eb && eb[0] == '1'; /* measured at 257^3, k = 3: 0.741-0.746 ms per sample with it, 0.737-0.745 without (one launch less per level, but blocks of 1024 rows with the update's and the sums' fetch chains one behind the other): not the default */
+    const int e = pmg_switch(PMG_SW_LRC_FUSED); /* '1': both fusions; '2': the noise term only; '3': the restore only */
+    l->unfused         = e != '1';
+    l->unfused_rhs     = e != '1' && e != '2';
+    l->unfused_restore = e != '1' && e != '3';
+    l->restore_in_btx  = l->unfused_restore && pmg_switch(PMG_SW_LRC_RESTORE) != '0';
+    l->reduce_in_axpy  = pmg_switch(PMG_SW_LRC_REDUCE) != '0';
+    l->bty_in_post     = pmg_switch(PMG_SW_LRC_BTY) == '1'; /* measured at 257^3, k = 3: 0.741-0.746 ms per sample with it, 0.737-0.745 without (one launch less per level, but blocks of 1024 rows with the update's and the sums' fetch chains one behind the other): not the default */
   }
   double sq[64];
   for (int c = 0; c < k; ++c) sq[c] = sqrt(fabs(S_host[c])); /* VecSqrtAbs(sqrtS), src/pc_mcgibbs.c:240-242 */
@@ -249,7 +246,7 @@ pmg_status pmg_lrc_build_dev(pmg_lrc *out, int32_t k, int64_t ld, const double *
   free(T);
   free(Sb);
   pmg_dev_free(Sb_dev);
-  if (!st && !getenv("PMG_LRC_DENSE")) st = lrc_compact(l);
+  if (!st && !pmg_switch(PMG_SW_LRC_DENSE)) st = lrc_compact(l);
   if (st) {
     pmg_lrc_destroy(&l);
     return st;

@@ -123,11 +123,7 @@ static pmg_status color_iterated(pmg_mcsor mc)
    Returns the visiting sequence (malloc'ed) or NULL for the natural order.  PMG_SELL_LOCALITY=0 never, 2 always. */
 static int32_t *locality_order(int32_t n, const int32_t *rowptr, const int32_t *colidx)
 {
-  static int env = -1;
-  if (env < 0) {
-    const char *e = getenv("PMG_SELL_LOCALITY");
-    env           = e ? atoi(e) : 1;
-  }
+  const int env = pmg_switch(PMG_SW_SELL_LOCALITY);
   if (!env || n < 4096) return NULL; /* small matrices live in the L2 whatever their numbering */
   int32_t *order = (int32_t *)malloc(sizeof(int32_t) * (size_t)n), *rank = (int32_t *)malloc(sizeof(int32_t) * (size_t)n);
   if (!order || !rank) {

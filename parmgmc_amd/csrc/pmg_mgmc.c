@@ -26,21 +26,14 @@
  */
 #include "pmg_mgmc_internal.h"
 
-/* the process-wide switches that choose a level's kernels inside the cycle: each is read here and nowhere else, once per
-   process, at its first use */
-static int env_int(const char *e, int dflt) { return e ? atoi(e) : dflt; }
-static int sw_st27_pair(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_ST27_PAIR"), 1); return v; }
-static int sw_st27_pair_slab(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_ST27_PAIR_SLAB"), 1); return v; } /* probes: 2 = paired residual only, 3 = paired sweeps only */
-static int sw_prolong_both(void) { static int v = -1; if (v < 0) v = getenv("PMG_MG_PROLONG_BOTH") != NULL; return v; }
-static int sw_fused_zero(void) { static int v = -1; if (v < 0) v = env_int(getenv("PMG_MG_FUSED_ZERO"), 1); return v; }
-
 /* the phase-fused out-of-place sweep and the paired residual (kernels_stencil27_pair.hip) serve class-stencil levels
    that live on one device; PMG_ST27_PAIR=0 keeps the one-launch-per-colour kernels (same bits) */
-static int st27_use_pair(const mg_level *Lv) { return sw_st27_pair() && Lv->is_st27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz; }
+static int st27_use_pair(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR) && Lv->is_st27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz; }
 
 /* the same kernels on the z-slab of a distributed class-stencil level: one launch per z-parity phase instead of four, the
-   halo of the boundary planes behind each as before; PMG_ST27_PAIR_SLAB=0 keeps the per-colour kernels (same bits) */
-static int st27_use_pair_slab(const mg_level *Lv) { return sw_st27_pair_slab() && Lv->is_st27 && Lv->distributed; }
+   halo of the boundary planes behind each as before; PMG_ST27_PAIR_SLAB=0 keeps the per-colour kernels (same bits; probes:
+   2 = paired residual only, 3 = paired sweeps only) */
+static int st27_use_pair_slab(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR_SLAB) && Lv->is_st27 && Lv->distributed; }
 
 /* the level's own iterate is swept out of place, into Lv->x2 */
 int pmg_mgmc_i_st27_out_of_place(const mg_level *Lv) { return Lv->x2 && st27_use_pair(Lv); }
@@ -157,7 +150,7 @@ static pmg_status st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double
     Lv->x_unset = 0;
     return PMG_SUCCESS;
   }
-  const int pp  = Lv->x2 && st27_use_pair_slab(Lv) && sw_st27_pair_slab() != 2; /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
+  const int pp  = Lv->x2 && st27_use_pair_slab(Lv) && pmg_switch(PMG_SW_ST27_PAIR_SLAB) != 2; /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
   double   *out = pp ? Lv->x2 : Lv->x;
   for (int phase = 0; phase < 2; ++phase) {
     if (pp) PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, phase, h->omega, 1, seed, *ctr, rhs, Lv->x, out, stream));
@@ -244,7 +237,7 @@ pmg_status pmg_mgmc_i_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coar
     /* inside a cycle on one device the restriction also sets the zero guess of the coarse level: its rows are the rows of P^T, the
        padding of the layout is never written (zero since the allocation) -- one fill kernel less per level (PMG_MG_FUSED_ZERO=0) */
     const int needs_zero = l - 1 >= 1 || h->coarse_type != 0;
-    double   *zero = sw_fused_zero() && needs_zero && !h->dist && !Lv->dm && !Cc->dm && b_coarse == Cc->b && Cc->mc && Lv->R_nrows == Cc->n ? Cc->x : NULL;
+    double   *zero = pmg_switch(PMG_SW_MG_FUSED_ZERO) && needs_zero && !h->dist && !Lv->dm && !Cc->dm && b_coarse == Cc->b && Cc->mc && Lv->R_nrows == Cc->n ? Cc->x : NULL;
     PMG_KERNEL(pmgk_csr_spmv_rows(Lv->R_nrows, Lv->R_rowpos, Lv->R_rowptr, Lv->R_col, Lv->R_val, r_fine, b_coarse, 0, zero, stream));
     if (zero) Cc->x_zeroed = 1;
     if (Lv->dm && l == h->rb_fold) PMG_CALL(pmg_mgmc_i_rb_fold_allgather(h, b_coarse, stream)); /* the replicated level below: every rank needs the whole right-hand side */
@@ -314,10 +307,7 @@ pmg_status pmg_mgmc_i_prolong_add(pmg_mgmc h, int l, const double *e_coarse, dou
 #define MG_ETA_STRIDE 64
 static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_t *ctr, int on, void *stream)
 {
-  if (!h->eta_batch_mode) {
-    const char *e     = getenv("PMG_LRC_BATCH");
-    h->eta_batch_mode = (e && !atoi(e)) ? -1 : 1;
-  }
+  if (!h->eta_batch_mode) h->eta_batch_mode = pmg_switch(PMG_SW_LRC_BATCH) ? 1 : -1;
   const int env = h->eta_batch_mode > 0;
   const int top = h->nlevels - 1;
   uint64_t  seeds[PMGK_NORMAL_BATCH_MAX], ctrs[PMGK_NORMAL_BATCH_MAX];
@@ -370,7 +360,7 @@ static mg_path level_path(const struct pmg_mgmc_s *h, int l, int top_has_guess)
   mg_path         p  = {mg_level_lrc(Lv), level_rows(Lv), MG_GUESS_FILL, MG_RR_TWO, 0, 0, -1};
   if (l == 0 ? h->coarse_type == 0 : (l == h->nlevels - 1 && top_has_guess)) p.zero_guess = MG_GUESS_KEEP;
   else if (l >= 1 && pmg_mgmc_i_st27_out_of_place(Lv) && h->nu >= 1) p.zero_guess = MG_GUESS_UNSET; /* (also under a low-rank update: the noise term changes b, the repair acts on the swept iterate) */
-  p.residual_pair = st27_use_pair(Lv) || (st27_use_pair_slab(Lv) && sw_st27_pair_slab() != 3);
+  p.residual_pair = st27_use_pair(Lv) || (st27_use_pair_slab(Lv) && pmg_switch(PMG_SW_ST27_PAIR_SLAB) != 3);
   if (l == 0) return p;
   const mg_level *Cc = &h->lv[l - 1];
   if (Lv->is_grid && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused) {
@@ -383,7 +373,7 @@ static mg_path level_path(const struct pmg_mgmc_s *h, int l, int top_has_guess)
   p.rr_lowrank_restricted = p.rr != MG_RR_TWO && p.lrc;
   /* with omega = 1 a colour sweep never reads the old values of the colour it updates (the (1-omega) x term is
      gone), so the colour the post-smoother visits first needs no correction: it is overwritten unread */
-  if (Lv->grid_transfer && h->omega == 1.0 && h->nu >= 1 && !sw_prolong_both()) p.prolong_colour = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 0 : 1;
+  if (Lv->grid_transfer && h->omega == 1.0 && h->nu >= 1 && !pmg_switch(PMG_SW_MG_PROLONG_BOTH)) p.prolong_colour = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 0 : 1;
   return p;
 }
 

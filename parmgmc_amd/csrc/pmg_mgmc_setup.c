@@ -894,7 +894,7 @@ static pmg_status stencil_attach_lowrank(pmg_mgmc h, setup_scratch *s)
 static pmg_status slab_agree_fused_rr(pmg_mgmc h, int l)
 {
   mg_level *Lv = &h->lv[l];
-  if (!(l >= 1 && Lv->is_grid && Lv->distributed && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused && (!h->lrc_k || (Lv->lrc && h->lv[l - 1].lrc)) && !(getenv("PMG_GRID_FUSED_RR_SLAB") && !atoi(getenv("PMG_GRID_FUSED_RR_SLAB"))))) return PMG_SUCCESS;
+  if (!(l >= 1 && Lv->is_grid && Lv->distributed && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused && (!h->lrc_k || (Lv->lrc && h->lv[l - 1].lrc)) && pmg_switch(PMG_SW_GRID_FUSED_RR_SLAB))) return PMG_SUCCESS;
   const int32_t *fc = h->cuts + (size_t)l * (size_t)(h->nranks + 1), *cc = h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1);
   int            ok = 1;
   for (int r = 0; r < h->nranks; ++r) ok = ok && fc[r + 1] - fc[r] >= 2 && cc[r + 1] - cc[r] >= 1;
@@ -940,9 +940,8 @@ static pmg_status setup_stencil_body(pmg_mgmc h, setup_scratch *s)
   F->grid_transfer = 1;
   if (h->dist) { /* which levels stay distributed */
     const int nr1 = h->nranks + 1;
-    int64_t   cap = 0, rep = (int64_t)1 << 19;
+    int64_t   cap = 0, rep = pmg_switch_wide(PMG_SW_MG_REPLICATE_BELOW); /* default 2^19 */
     PMG_CALL(pmg_dist_get_info(h->dist, NULL, NULL, &cap));
-    if (getenv("PMG_MG_REPLICATE_BELOW")) rep = atoll(getenv("PMG_MG_REPLICATE_BELOW"));
     F->distributed = h->nranks > 1;
     int replicated = !F->distributed;
     for (int l = top - 1; l >= 0; --l) {
@@ -983,7 +982,7 @@ static pmg_status setup_stencil_body(pmg_mgmc h, setup_scratch *s)
 static pmg_status setup_dmda_body(pmg_mgmc h, setup_scratch *s)
 {
   const int top = h->nlevels - 1;
-  const int full_galerkin = getenv("PMG_MG_FULL_GALERKIN") != NULL, no_stencil = getenv("PMG_MG_NO_STENCIL") != NULL, csr_transfers = getenv("PMG_MG_CSR_TRANSFERS") != NULL;
+  const int full_galerkin = pmg_switch(PMG_SW_MG_FULL_GALERKIN), no_stencil = pmg_switch(PMG_SW_MG_NO_STENCIL), csr_transfers = pmg_switch(PMG_SW_MG_CSR_TRANSFERS);
   if (h->dist) PMG_CHECK(!h->keep_host, PMG_ERR_SUP, "host copies of the level matrices are a single-device feature");
   if (h->dist || (!h->keep_host && !full_galerkin && !no_stencil && !csr_transfers)) {
     /* class-stencil tables from the proxy hierarchy: no product with the full-size matrices */

@@ -105,9 +105,11 @@ def test_plane_pair_kernel_is_selected_where_stated(runs):
 
 
 def test_the_switch_is_read_and_documented():
-    """the library reads PMG_GRID_PLANE_PAIR and INTEGRATION.md section 5 lists it (what test_runtime_switch_inventory.py asks
-    of the switches it finds; the A/B above is what holds this one to the default's bits)"""
-    src = (HERE.parent / "parmgmc_amd" / "csrc" / "kernels_grid.hip").read_text()
-    assert re.search(r'grid_plane_pair_key\s*=\s*"PMG_GRID_PLANE_PAIR"', src) and "getenv(grid_plane_pair_key)" in src
+    """PMG_GRID_PLANE_PAIR is a row of the library's switch table, the grid launcher reads that row, and INTEGRATION.md
+    section 5 lists it (what test_runtime_switch_inventory.py asks of every row; the A/B above is what holds this one to the
+    default's bits)"""
+    csrc = HERE.parent / "parmgmc_amd" / "csrc"
+    assert re.search(r'^\s*\[PMG_SW_GRID_PLANE_PAIR\]\s*=\s*\{"PMG_GRID_PLANE_PAIR",', (csrc / "pmg_switch.c").read_text(), re.M)
+    assert "pmg_switch(PMG_SW_GRID_PLANE_PAIR)" in (csrc / "kernels_grid.hip").read_text()
     sec5 = re.search(r"^## 5\..*?(?=^## 6\.)", (HERE.parent / "INTEGRATION.md").read_text(), re.S | re.M).group(0)
     assert "`PMG_GRID_PLANE_PAIR=0`" in sec5

@@ -1,6 +1,7 @@
-"""Every PMG_* environment switch the native library reads is documented in INTEGRATION.md section 5, and every switch
-there that claims to leave results alone is held to that by a test: a configuration of test_gpu_switches.py, or the
-existing test named in PINNED_ELSEWHERE (which must mention the switch)."""
+"""Every PMG_* environment switch the native library reads is a row of the table in csrc/pmg_switch.c, which alone reads the
+environment, and is documented in INTEGRATION.md section 5, and every switch there that claims to leave results alone is
+held to that by a test: a configuration of test_gpu_switches.py, or the existing test named in PINNED_ELSEWHERE (which
+must mention the switch)."""
 import re
 from pathlib import Path
 
@@ -29,14 +30,17 @@ PINNED_ELSEWHERE = {
     "PMG_ST27_PAIR_SLAB": "tests/test_gpu_dist_two_ranks.py",
     "PMG_GRID_FUSED_RR_SLAB": "tests/test_gpu_dist_two_ranks.py",
     "PMG_DISTMCSOR_REFRESH_BY_COLOUR": "tests/test_gpu_rowblock_c.py",
+    "PMG_GRID_PLANE_PAIR": "tests/test_gpu_grid_plane_pair.py",
 }
 
 
+def table_rows():
+    """(id, name) of every row of the switch table: `[PMG_SW_X] = {"PMG_X", kind, default, read time}`"""
+    return re.findall(r'^\s*\[(PMG_SW_[A-Z0-9_]+)\]\s*=\s*\{"(PMG_[A-Z0-9_]+)",', (CSRC / "pmg_switch.c").read_text(), re.M)
+
+
 def native_switches():
-    names = set()
-    for f in sorted(CSRC.glob("*.c")) + sorted(CSRC.glob("*.hip")):
-        names |= set(re.findall(r'getenv\(\s*"(PMG_[A-Z0-9_]+)"', f.read_text()))
-    return names
+    return {name for _, name in table_rows()}
 
 
 def section5():
@@ -72,3 +76,27 @@ def test_every_result_path_switch_is_pinned():
 
 def test_switch_table_names_only_real_switches():
     assert not sorted(switches_under_test() - native_switches())
+
+
+def test_only_the_table_reads_the_environment():
+    for d in (CSRC, ROOT / "include", ROOT / "examples"):
+        for f in sorted(p for p in d.rglob("*") if p.is_file() and p.suffix in (".c", ".h", ".hip", ".hpp", ".inc", ".cpp")):
+            if f == CSRC / "pmg_switch.c":
+                continue
+            text = f.read_text()
+            assert not re.search(r"getenv\s*\([^)]*PMG_", text), f"{f.name} reads a PMG_ variable by itself"
+            if d == CSRC:  # nor through a name held elsewhere: a switch of the library is a row of the table
+                assert not re.search(r"getenv\s*\(", text), f"{f.name} calls getenv"
+    # the table passes its names to getenv and holds no name outside its rows
+    text = (CSRC / "pmg_switch.c").read_text()
+    assert text.count("getenv(") == 1 and "getenv(pmg_switch_row[id].name)" in text
+    assert len(re.findall(r'"PMG_[A-Z0-9_]+"', text)) == len(table_rows())
+
+
+def test_ids_and_rows_correspond_one_to_one():
+    header = (CSRC / "pmg_switch.h").read_text()
+    ids = re.findall(r"PMG_SW_[A-Z0-9_]+", re.search(r"typedef enum \{(.*?)\} pmg_switch_id;", header, re.S).group(1))
+    assert ids[-1] == "PMG_SW_COUNT" and len(set(ids)) == len(ids)
+    rows = table_rows()
+    assert [i for i, _ in rows] == ids[:-1], "one row per id, in the order of the enum"
+    assert all(name == "PMG_" + i[len("PMG_SW_"):] for i, name in rows) and len({n for _, n in rows}) == len(rows)

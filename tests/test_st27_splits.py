@@ -36,7 +36,8 @@ def test_restated_constants_are_the_kernels():
     assert "if (env && 64 / segw >= 2)" in pair and "P.nseg     = 64 / segw" in pair
     assert "return (unsigned)(8 * nbx * ((T + 7) / 8));" in pair
     plane = (CSRC / "kernels_stencil27.hip").read_text()
-    assert int(re.search(r"plane_limit\s*=\s*e \? atoi\(e\) : (\d+);", plane).group(1)) == M.PLANE_LIMIT
+    assert int(re.search(r'\{"PMG_ST27_PHASE_MAX_PLANE", INT, (\d+), PROCESS\}', (CSRC / "pmg_switch.c").read_text()).group(1)) == M.PLANE_LIMIT  # the default: its row of the switch table
+    assert "plane_limit = pmg_switch(PMG_SW_ST27_PHASE_MAX_PLANE);" in plane
     assert "(int64_t)S->nx * S->ny <= plane_limit" in plane and "dim3(cz), dim3(1024)" in plane
 
 
