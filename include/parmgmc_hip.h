@@ -24,6 +24,15 @@
  *     first call of its kind on the object, a larger nchains, the first per-chain right-hand side) or to replace the
  *     seeds of a chains call synchronises `stream`, and returns only when the new buffers are zero-filled; with the
  *     sizes and seeds of an earlier call nothing synchronises.
+ *   - a call's results depend on how the object was built, on its current settings and on the call's arguments only --
+ *     not on the calls made before it: workspaces, uploaded seeds, noise drawn ahead and lazily rebuilt tables never
+ *     show.  A failing call leaves the object usable and its later results unchanged.  (The noise counter of a PC and
+ *     the running sums of pmg_chainstats / pmg_chaincov are state by design: pmg_pc_set_noise_counter and the reset
+ *     calls set them.)
+ *   - on objects with a row-compact low-rank update (pmg_*_set_lowrank with B on few rows), the `const` right-hand side
+ *     of a sampling call in the object's own layout is written (the noise term on B's support rows) and restored in
+ *     place, bit for bit, by work queued on `stream`: the caller must not read it from another stream while the call's
+ *     work is in flight.
  *   - objects are not thread safe (the reference is single threaded per rank, src/parmgmc.c:38-42).
  */
 #ifndef PARMGMC_HIP_H
@@ -166,6 +175,9 @@ pmg_status pmg_mcsor_sweep_color_layout(pmg_mcsor mc, int32_t color, int noisy, 
    y -= Bb (B^T y) (:101-112) and every noisy right-hand side gets + B (sqrt(S) o eta) (src/pc_mcgibbs.c:130-140,
    src/pc_sorgibbs.c:86-90).  k = 0 removes the update. */
 pmg_status pmg_mcsor_set_lowrank(pmg_mcsor mc, int32_t k, const double *B_host, const double *S_host);
+/* how the update is kept: its rank (0 = none) and the rows its passes run over -- the support rows of the row-compact form
+   (the form that writes the noise term into the right-hand side in place), every layout row of the dense form (*dense = 1) */
+pmg_status pmg_mcsor_lowrank_sizes(pmg_mcsor mc, int32_t *k, int64_t *rows, int *dense);
 /* MCSORDestroy (src/mc_sor.c:60-90); *mc = NULL afterwards; NULL handle is a no-op. */
 pmg_status pmg_mcsor_destroy(pmg_mcsor *mc);
 
@@ -214,6 +226,7 @@ pmg_status pmg_grid_sweep_color_planes_cvec(pmg_grid g, int color, int32_t kbegi
 pmg_status pmg_grid_halo_plane(pmg_grid g, int color, int side, int64_t *owned_offset, int64_t *ghost_offset, int64_t *count);
 /* the same MATLRC update for the grid operator (B in DMDA natural order); single-device grids */
 pmg_status pmg_grid_set_lowrank(pmg_grid g, int32_t k, const double *B_host, const double *S_host);
+pmg_status pmg_grid_lowrank_sizes(pmg_grid g, int32_t *k, int64_t *rows, int *dense); /* as pmg_mcsor_lowrank_sizes */
 /* Sample loop on natural-order vectors: converts in once, runs `its` sweeps, converts out once. */
 pmg_status pmg_grid_sample(pmg_grid g, const double *b_nat_dev, double *y_nat_dev, int32_t its, int scaled, uint64_t seed, uint64_t counter0, uint64_t *counter_out, void *stream);
 pmg_status pmg_grid_destroy(pmg_grid *g);

@@ -346,6 +346,13 @@ pmg_status pmg_grid_residual_cvec(pmg_grid g, const double *b, const double *y, 
 
 pmg_lrc pmg_grid_lrc(pmg_grid g) { return g ? g->lrc : NULL; }
 
+pmg_status pmg_grid_lowrank_sizes(pmg_grid g, int32_t *k, int64_t *rows, int *dense)
+{
+  PMG_CHECK(g && k && rows && dense, PMG_ERR_ARG_NULL, "null argument");
+  pmg_lrc_get_sizes(g->lrc, k, rows, dense);
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_grid_residual_restrict(pmg_grid g, const double *b, const double *y, const double *ylo2, const double *yhi2, const pmgk_st27_dims *C, double *b_coarse, int *done, void *stream)
 {
   PMG_CHECK(g && b && y && C && b_coarse && done, PMG_ERR_ARG_NULL, "null argument");

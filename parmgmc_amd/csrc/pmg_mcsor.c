@@ -765,6 +765,13 @@ pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc)
 
 pmg_lrc pmg_mcsor_lrc(pmg_mcsor mc) { return mc ? mc->lrc : NULL; }
 
+pmg_status pmg_mcsor_lowrank_sizes(pmg_mcsor mc, int32_t *k, int64_t *rows, int *dense)
+{
+  PMG_CHECK(mc && k && rows && dense, PMG_ERR_ARG_NULL, "null argument");
+  pmg_lrc_get_sizes(mc->lrc, k, rows, dense);
+  return PMG_SUCCESS;
+}
+
 const int32_t *pmg_mcsor_orig_dev(pmg_mcsor mc) { return mc->S.orig; }
 
 /* one directional sweep over all colours on C chains */

@@ -148,6 +148,12 @@ class MCSOR:
         S = np.ascontiguousarray(S, np.float64)
         check(lib.pmg_mcsor_set_lowrank(self._h, B.shape[1], B.ctypes.data, S.ctypes.data))
 
+    def lowrank_sizes(self):
+        """(k, rows, dense): rank of the update (0: none) and the rows its passes run over; dense False = the row-compact form"""
+        k, rows, dense = C.c_int32(), C.c_int64(), C.c_int()
+        check(lib.pmg_mcsor_lowrank_sizes(self._h, C.byref(k), C.byref(rows), C.byref(dense)))
+        return k.value, rows.value, bool(dense.value)
+
     def destroy(self):
         if self._h:
             check(lib.pmg_mcsor_destroy(C.byref(self._h)))
@@ -243,6 +249,12 @@ class GridMCSOR:
         B = np.asfortranarray(B, dtype=np.float64)
         S = np.ascontiguousarray(S, np.float64)
         check(lib.pmg_grid_set_lowrank(self._h, B.shape[1], B.ctypes.data, S.ctypes.data))
+
+    def lowrank_sizes(self):
+        """(k, rows, dense) as MCSOR.lowrank_sizes"""
+        k, rows, dense = C.c_int32(), C.c_int64(), C.c_int()
+        check(lib.pmg_grid_lowrank_sizes(self._h, C.byref(k), C.byref(rows), C.byref(dense)))
+        return k.value, rows.value, bool(dense.value)
 
     def residual_cvec(self, b, y, r):
         check(lib.pmg_grid_residual_cvec(self._h, _ptr(b), _ptr(y), _ptr(r), _stream()))
