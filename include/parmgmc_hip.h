@@ -162,7 +162,8 @@ pmg_status pmg_mcsor_sample_chains_rhs(pmg_mcsor mc, int32_t nchains, const uint
 /* Building blocks of the ROW-BLOCK distributed sampler (MCSORApply_MPIAIJ, src/mc_sor.c:298-381: for every colour,
    update the ghost values, then sweep the colour's rows): a rank holds its rows with the off-process columns appended
    as ghost rows (identity rows in an extra, never swept colour); the caller moves ghost values between the per-colour
-   sweeps (parmgmc_amd/dist.py: DistMCSOR over torch.distributed).  row0 = global index of local row 0, so that the
+   sweeps (pmg_distmcsor.c; parmgmc_amd/dist.py: DistMCSOR over torch.distributed as the fall-back -- both from the plan of
+   pmg_rowblock_plan_create).  row0 = global index of local row 0, so that the
    noise is that of the global row and the chain is the single-process chain bit for bit. */
 pmg_status pmg_mcsor_set_noise_row_offset(pmg_mcsor mc, int64_t row0);
 /* on != 0: idiag = omega / d in ONE rounding, PCPARSOR's rule (LocalMatInvertDiagonalForSOR, src/pc_parsor.c:53-86), instead
@@ -512,7 +513,8 @@ pmg_status pmg_mgmc_destroy(pmg_mgmc *mg);
 /* The ONE collective the set-up needs from its caller: a byte all-gather of equal-sized blocks over the ranks of the
    matrix' communicator (recv holds nranks * nbytes, block r from rank r; 0 = success).  A PETSc adapter passes
      int ag(void *ctx, const void *s, int64_t n, void *r) { return MPI_Allgather(s, (int)n, MPI_BYTE, r, (int)n, MPI_BYTE, *(MPI_Comm *)ctx); }
-   (adapter/hip_petsc_common.h), the Python tests torch.distributed, examples/pmg_bench.c pipes between forked ranks.
+   (adapter/hip_petsc_common.h), parmgmc_amd/dist.py torch.distributed (DistMCSOR and DistAIJMGMC take their plans and
+   hierarchies from here too), examples/pmg_bench.c pipes between forked ranks.
    Every function that takes a pmg_host_comm is COLLECTIVE over its ranks; a failure on one rank fails on all. */
 typedef int (*pmg_allgather_fn)(void *ctx, const void *send, int64_t nbytes, void *recv);
 typedef struct {

@@ -349,21 +349,18 @@ def torch_host_comm(rank: int, world: int, group=None):
             import torch
             import torch.distributed as dist
 
-            src = np.ctypeslib.as_array(C.cast(send, C.POINTER(C.c_uint8)), shape=(max(int(nbytes), 1),))[: int(nbytes)]
-            dev = "cuda" if dist.get_backend(group) == "nccl" else "cpu"
-            t = torch.from_numpy(src.copy()).to(dev)
-            out = torch.empty(world * int(nbytes), dtype=torch.uint8, device=dev)
-            if nbytes:
-                if dev == "cuda":
-                    dist.all_gather_into_tensor(out, t, group=group)
-                else:
-                    parts = [torch.empty(int(nbytes), dtype=torch.uint8) for _ in range(world)]
-                    dist.all_gather(parts, t, group=group)
-                    out = torch.cat(parts)
-                dst = np.ctypeslib.as_array(C.cast(recv, C.POINTER(C.c_uint8)), shape=(world * int(nbytes),))
-                dst[:] = out.cpu().numpy()
-            else:
+            nb = int(nbytes)
+            if not nb:
                 dist.barrier(group=group)
+                return 0
+            src = torch.from_numpy(np.ctypeslib.as_array(C.cast(send, C.POINTER(C.c_uint8)), shape=(nb,)))
+            dst = torch.from_numpy(np.ctypeslib.as_array(C.cast(recv, C.POINTER(C.c_uint8)), shape=(world * nb,)))
+            if dist.get_backend(group) == "nccl":
+                out = torch.empty(world * nb, dtype=torch.uint8, device="cuda")
+                dist.all_gather_into_tensor(out, src.cuda(), group=group)
+                dst.copy_(out)
+            else:  # gloo gathers straight into the caller's buffer
+                dist.all_gather(list(dst.split(nb)), src, group=group)
             return 0
         except Exception:  # pragma: no cover
             import traceback

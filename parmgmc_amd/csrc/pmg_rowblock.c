@@ -17,8 +17,9 @@
  *   pmg_dist_create_comm        the ipc / RCCL transport bootstrapped through the caller's byte all-gather
  *
  * Everything collective goes through ONE callback, a fixed-size byte all-gather (pmg_host_comm): MPI_Allgather in a PETSc
- * adapter, torch.distributed in the Python tests, pipes in examples/pmg_bench.c.  The plans are pinned index for index to
- * the Python builders of round 2 (parmgmc_amd/dist.py: rowblock_plan, rowblock_hierarchy) by tests/test_rowblock_c.py. */
+ * adapter, torch.distributed in parmgmc_amd/dist.py, pipes in examples/pmg_bench.c.  This is the only implementation of the
+ * set-up; tests/test_rowblock_c.py pins it index for index to an independent numpy / scipy statement of the same plans and
+ * slicing (tests/rowblock_reference.py: rowblock_plan, rowblock_hierarchy). */
 #include "pmg_internal.h"
 #include <stdlib.h>
 #include <string.h>
@@ -103,11 +104,34 @@ static int cmp_i64(const void *a, const void *b)
   return (x > y) - (x < y);
 }
 
-/* sort + unique in place; returns the new length */
+/* sort + unique in place; returns the new length.  The off-block columns of a level are a large part of its entries when
+   the numbering is not local (uniform refinement appends the new vertices), and qsort through a comparison callback was
+   a quarter of the set-up's host time: long arrays take an LSD radix sort, 16 bits a pass, over the digits the keys differ in */
 static int64_t sort_unique(int64_t *v, int64_t n)
 {
   if (n <= 0) return 0;
-  qsort(v, (size_t)n, sizeof(int64_t), cmp_i64);
+  int64_t  *t   = n >= 256 ? (int64_t *)malloc(sizeof(int64_t) * (size_t)n) : NULL;
+  uint32_t *cnt = t ? (uint32_t *)malloc(sizeof(uint32_t) * 65536) : NULL;
+  if (cnt && n < UINT32_MAX) {
+    uint64_t diff = 0;
+    for (int64_t i = 1; i < n; ++i) diff |= (uint64_t)(v[i] ^ v[0]);
+    int64_t *src = v, *dst = t;
+    for (int shift = 0; shift < 64; shift += 16) {
+      if (!((diff >> shift) & 0xffff)) continue;
+      const uint64_t flip = shift == 48 ? 0x8000 : 0; /* the sign bit: negative keys first */
+      memset(cnt, 0, sizeof(uint32_t) * 65536);
+      for (int64_t i = 0; i < n; ++i) cnt[(((uint64_t)src[i] >> shift) & 0xffff) ^ flip]++;
+      for (uint32_t d = 0, at = 0; d < 65536; ++d) {
+        const uint32_t k = cnt[d];
+        cnt[d] = at, at += k;
+      }
+      for (int64_t i = 0; i < n; ++i) dst[cnt[(((uint64_t)src[i] >> shift) & 0xffff) ^ flip]++] = src[i];
+      int64_t *s = src;
+      src = dst, dst = s;
+    }
+    if (src != v) memcpy(v, src, sizeof(int64_t) * (size_t)n);
+  } else qsort(v, (size_t)n, sizeof(int64_t), cmp_i64);
+  free(t), free(cnt);
   int64_t m = 1;
   for (int64_t i = 1; i < n; ++i)
     if (v[i] != v[m - 1]) v[m++] = v[i];
@@ -124,6 +148,31 @@ static int64_t bsearch_i64(const int64_t *v, int64_t n, int64_t x)
     else hi = mid;
   }
   return lo < n && v[lo] == x ? lo : -1;
+}
+
+/* index of a global row in a sorted array of rows, asked once per matrix entry: through a direct table over the n global rows
+   where that is affordable (bisection per entry was, with the sorting above, most of the set-up's host time), by bisection
+   otherwise */
+typedef struct {
+  const int64_t *v;
+  int64_t        len, n;
+  int32_t       *at; /* at[g] = index of g in v, or -1; NULL: bisection */
+} row_finder;
+
+static void finder_init(row_finder *f, const int64_t *v, int64_t len, int64_t n)
+{
+  f->v = v, f->len = len, f->n = n;
+  f->at = len > 0 && len < INT32_MAX && n > 0 && n <= ((int64_t)1 << 26) ? (int32_t *)malloc(sizeof(int32_t) * (size_t)n) : NULL;
+  if (!f->at) return;
+  memset(f->at, 0xff, sizeof(int32_t) * (size_t)n);
+  for (int64_t q = 0; q < len; ++q)
+    if (v[q] >= 0 && v[q] < n) f->at[v[q]] = (int32_t)q;
+}
+
+static int64_t finder_index(const row_finder *f, int64_t x)
+{
+  if (!f->at) return bsearch_i64(f->v, f->len, x);
+  return x >= 0 && x < f->n ? f->at[x] : -1;
 }
 
 /* rank that owns global row g: starts[r] <= g < starts[r+1] */
@@ -179,6 +228,7 @@ struct pmg_rowblock_plan_s {
   int32_t  rank, nranks, ncolors, nloc, nghost;
   int64_t  row0;
   int64_t *ghosts;    /* nghost sorted global rows: local row nloc + q */
+  row_finder ghost_at; /* global row -> q */
   int64_t *send_ptr;  /* ncolors + 1 */
   int32_t *send_rows; /* local OWNED rows this rank contributes per colour, by ascending global row */
   int64_t *counts;    /* [ncolors][nranks]: length of every rank's list of a colour */
@@ -191,7 +241,7 @@ void pmg_rowblock_plan_destroy(pmg_rowblock_plan *pp)
 {
   if (!pp || !*pp) return;
   pmg_rowblock_plan p = *pp;
-  free(p->ghosts), free(p->send_ptr), free(p->send_rows), free(p->counts), free(p->recv_ptr), free(p->recv_src), free(p->recv_rows);
+  free(p->ghost_at.at), free(p->ghosts), free(p->send_ptr), free(p->send_rows), free(p->counts), free(p->recv_ptr), free(p->recv_src), free(p->recv_rows);
   free(p);
   *pp = NULL;
 }
@@ -348,6 +398,7 @@ done:
     pmg_rowblock_plan_destroy(&p);
     return st;
   }
+  finder_init(&p->ghost_at, p->ghosts, p->nghost, n);
   *out = p;
   return PMG_SUCCESS;
 }
@@ -387,7 +438,7 @@ static pmg_status rowblock_check_coloring(const pmg_rowblock_plan p, const int64
       int32_t cc;
       if (c >= r0 && c < r0 + nloc) cc = colors_owned[c - r0];
       else {
-        const int64_t q = bsearch_i64(p->ghosts, p->nghost, c);
+        const int64_t q = finder_index(&p->ghost_at, c);
         cc              = q >= 0 ? gcol[q] : -1;
       }
       if (cc == colors_owned[i]) st = pmg_set_error(PMG_ERR_ARG_WRONG, __FILE__, __LINE__, "not a distance-1 colouring: rows %lld and %lld are coupled and both have colour %d", (long long)(r0 + i), (long long)c, (int)cc);
@@ -423,6 +474,7 @@ pmg_status pmg_rowblock_color_greedy(const pmg_host_comm *comm, const int64_t *r
   for (int64_t k = 0; k < rp[nloc]; ++k) nlow += ci[k] < r0;
   int64_t *low  = (int64_t *)malloc(sizeof(int64_t) * (size_t)(nlow > 0 ? nlow : 1));
   int32_t *lcol = NULL, *mark = NULL;
+  row_finder low_at = {0};
   int64_t *offs = (int64_t *)malloc(sizeof(int64_t) * (size_t)(np + 1));
   if (!low || !offs) st = pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of host memory");
   if (!st) {
@@ -431,6 +483,7 @@ pmg_status pmg_rowblock_color_greedy(const pmg_host_comm *comm, const int64_t *r
       if (ci[k] < r0) low[q++] = ci[k];
     nlow = sort_unique(low, nlow);
     lcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nlow > 0 ? nlow : 1));
+    finder_init(&low_at, low, nlow, row_starts[np]);
     if (!lcol) st = pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of host memory");
   }
   st = hc_agree(comm, st, "preparing the colouring");
@@ -451,7 +504,7 @@ pmg_status pmg_rowblock_color_greedy(const pmg_host_comm *comm, const int64_t *r
         for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
           const int64_t c = ci[k];
           int32_t       cc = -1;
-          if (c < r0) cc = lcol[bsearch_i64(low, nlow, c)];
+          if (c < r0) cc = lcol[finder_index(&low_at, c)];
           else if (c < r0 + i) cc = colors_owned[c - r0];
           if (cc >= 0 && cc <= maxdeg) mark[cc] = (int32_t)i; /* a colour above the row's degree cannot be the smallest free one */
         }
@@ -481,7 +534,7 @@ pmg_status pmg_rowblock_color_greedy(const pmg_host_comm *comm, const int64_t *r
       if (all[r] > nc) nc = all[r];
     free(all);
   }
-  free(low), free(lcol), free(offs);
+  free(low_at.at), free(low), free(lcol), free(offs);
   PMG_CALL(st);
   *ncolors = nc;
   return PMG_SUCCESS;
@@ -507,12 +560,14 @@ pmg_status pmg_rowblock_color_iterated(const pmg_host_comm *comm, const int64_t 
   int32_t *newc = (int32_t *)malloc(sizeof(int32_t) * (size_t)(nloc > 0 ? nloc : 1));
   int32_t *mark = (int32_t *)malloc(sizeof(int32_t) * (size_t)(maxdeg + 2));
   int32_t *gcol = NULL, *gown = NULL;
+  row_finder gh_at = {0};
   if (!gh || !offs || !newc || !mark) st = pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of host memory");
   if (!st) {
     int64_t q = 0;
     for (int64_t k = 0; k < rp[nloc]; ++k)
       if (ci[k] < r0 || ci[k] >= r1) gh[q++] = ci[k];
     ngh  = sort_unique(gh, ngh);
+    finder_init(&gh_at, gh, ngh, row_starts[np]);
     gcol = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ngh > 0 ? ngh : 1));
     gown = (int32_t *)malloc(sizeof(int32_t) * (size_t)(ngh > 0 ? ngh : 1));
     if (!gcol || !gown) st = pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of host memory");
@@ -531,7 +586,7 @@ pmg_status pmg_rowblock_color_iterated(const pmg_host_comm *comm, const int64_t 
       if (colors_owned[i] != cls) continue;
       for (int64_t k = rp[i]; k < rp[i + 1]; ++k) {
         const int64_t c  = ci[k];
-        const int32_t cc = c == r0 + i ? -1 : (c >= r0 && c < r1 ? newc[c - r0] : gcol[bsearch_i64(gh, ngh, c)]);
+        const int32_t cc = c == r0 + i ? -1 : (c >= r0 && c < r1 ? newc[c - r0] : gcol[finder_index(&gh_at, c)]);
         if (cc >= 0 && cc <= maxdeg) mark[cc] = (int32_t)i; /* a colour above the row's degree cannot be the smallest free one */
       }
       int32_t col = 0;
@@ -554,7 +609,7 @@ pmg_status pmg_rowblock_color_iterated(const pmg_host_comm *comm, const int64_t 
       if (all[r] > nc) nc = all[r];
     free(all);
   }
-  free(gh), free(offs), free(newc), free(mark), free(gcol), free(gown);
+  free(gh_at.at), free(gh), free(offs), free(newc), free(mark), free(gcol), free(gown);
   PMG_CALL(st);
   *ncolors = nc;
   return PMG_SUCCESS;
@@ -864,10 +919,10 @@ static pmg_status build_restriction(const pmg_host_comm *c, const gcsr *P, int64
 }
 
 /* global row -> local row of this rank on a row-block level (owned: g - row0; ghost: nloc + its rank among the ghosts) */
-static int64_t local_of(const rbh_level *L, const int64_t *ghosts, int32_t nghost, int64_t g)
+static int64_t local_of(const rbh_level *L, const pmg_rowblock_plan plan, int64_t g)
 {
   if (g >= L->row0 && g < L->row0 + L->nloc) return g - L->row0;
-  const int64_t q = bsearch_i64(ghosts, nghost, g);
+  const int64_t q = finder_index(&plan->ghost_at, g);
   return q < 0 ? -1 : L->nloc + q;
 }
 
@@ -952,7 +1007,6 @@ pmg_status pmg_rbh_build(pmg_rbh h)
   /* ---- local matrices ---- */
   for (int l = fold; l < L && !st; ++l) {
     rbh_level     *Lv = &h->lv[l];
-    const int64_t *gh = Lv->plan->ghosts;
     const int32_t  ng = Lv->plan->nghost;
     const int64_t  nnz = Lv->A.rp[Lv->nloc];
     Lv->nlocal         = (int32_t)(Lv->nloc + ng);
@@ -966,7 +1020,7 @@ pmg_status pmg_rbh_build(pmg_rbh h)
     if (!st) {
       for (int64_t r = 0; r <= Lv->nloc; ++r) Lv->l_rp[r] = (int32_t)Lv->A.rp[r];
       for (int64_t k = 0; k < nnz && !st; ++k) {
-        const int64_t lo = local_of(Lv, gh, ng, Lv->A.ci[k]);
+        const int64_t lo = local_of(Lv, Lv->plan, Lv->A.ci[k]);
         if (lo < 0) st = pmg_set_error(PMG_ERR_PLIB, __FILE__, __LINE__, "level %d: column %lld is neither owned nor a ghost", l, (long long)Lv->A.ci[k]);
         Lv->l_ci[k] = (int32_t)lo, Lv->l_v[k] = Lv->A.v[k];
       }
@@ -989,14 +1043,14 @@ pmg_status pmg_rbh_build(pmg_rbh h)
     if (!st) {
       for (int64_t r = 0; r <= Lv->P.nr; ++r) Lv->P_rp[r] = (int32_t)Lv->P.rp[r];
       for (int64_t k = 0; k < pnz && !st; ++k) {
-        const int64_t lo = rep ? Lv->P.ci[k] : local_of(Cc, Cc->plan->ghosts, Cc->plan->nghost, Lv->P.ci[k]);
+        const int64_t lo = rep ? Lv->P.ci[k] : local_of(Cc, Cc->plan, Lv->P.ci[k]);
         if (lo < 0) st = pmg_set_error(PMG_ERR_PLIB, __FILE__, __LINE__, "level %d: the interpolation reads coarse row %lld, neither owned nor a ghost", l, (long long)Lv->P.ci[k]);
         Lv->P_ci[k] = (int32_t)lo, Lv->P_v[k] = Lv->P.v[k];
       }
       Lv->R_nrows = (int32_t)R[l].nr;
       for (int64_t r = 0; r <= R[l].nr; ++r) Lv->R_rp[r] = (int32_t)R[l].rp[r];
       for (int64_t k = 0; k < rnz && !st; ++k) {
-        const int64_t lo = local_of(Lv, gh, ng, R[l].ci[k]);
+        const int64_t lo = local_of(Lv, Lv->plan, R[l].ci[k]);
         if (lo < 0) st = pmg_set_error(PMG_ERR_PLIB, __FILE__, __LINE__, "level %d: the restriction reads fine row %lld, neither owned nor a ghost", l, (long long)R[l].ci[k]);
         Lv->R_ci[k] = (int32_t)lo, Lv->R_v[k] = R[l].v[k];
       }
@@ -1047,8 +1101,8 @@ pmg_status pmg_rbh_get_level(pmg_rbh h, int32_t level, pmg_rbh_level_view *v)
   return pmg_rowblock_plan_get(L->plan, &v->nghost, &v->ghosts, &v->send_ptr, &v->send_rows, &v->counts, &v->recv_ptr, &v->recv_src, &v->recv_rows);
 }
 
-/* PCGAMGMC on the hierarchy: pmg_mgmc_create_hierarchy + every pmg_mgmc_set_level_* call (what parmgmc_amd.dist.DistAIJMGMC
-   does from Python).  `transport`: any pmg_dist object of the same ranks (pmg_dist_create_comm).  The arrays stay borrowed
+/* PCGAMGMC on the hierarchy: pmg_mgmc_create_hierarchy + every pmg_mgmc_set_level_* call, for the adapter
+   and for parmgmc_amd.dist.DistAIJMGMC / CRowBlock.mgmc alike.  `transport`: any pmg_dist object of the same ranks (pmg_dist_create_comm).  The arrays stay borrowed
    from `h` until pmg_mgmc_setup: destroy `h` after it. */
 pmg_status pmg_rbh_create_mgmc(pmg_rbh h, pmg_dist transport, pmg_mgmc *out)
 {
@@ -1125,7 +1179,7 @@ pmg_status pmg_rowblock_sampler_create(const pmg_host_comm *comm, pmg_dist trans
       memset(&tmp, 0, sizeof tmp);
       tmp.row0 = r0, tmp.nloc = nloc;
       for (int64_t r = 0; r <= nloc; ++r) rp[r] = (int32_t)A.rp[r];
-      for (int64_t k = 0; k < nnz; ++k) ci[k] = (int32_t)local_of(&tmp, plan->ghosts, ng, A.ci[k]), v[k] = A.v[k];
+      for (int64_t k = 0; k < nnz; ++k) ci[k] = (int32_t)local_of(&tmp, plan, A.ci[k]), v[k] = A.v[k];
       for (int32_t q = 0; q < ng; ++q) rp[nloc + q + 1] = (int32_t)(nnz + q + 1), ci[nnz + q] = (int32_t)(nloc + q), v[nnz + q] = 1.0;
       for (int64_t r = 0; r < nloc; ++r) lcol[r] = colors_owned[r];
       for (int32_t q = 0; q < ng; ++q) lcol[nloc + q] = ncolors;

@@ -462,6 +462,65 @@ class DistMGMC:
         self.grid_sampler = None
 
 
+def _c_rowblock_plan(rank: int, world: int, group, starts, ci, colors, ncolors: int):
+    """pmg_rowblock_plan_create for this rank's rows (ci: their global columns, int64; no transfer ghosts), read back with
+    pmg_rowblock_plan_get: (ghosts, dict(send_ptr, send_rows, counts[ncolors, world], recv_ptr, recv_src, recv_rows)) as
+    numpy copies.  Collective over `group`."""
+    import ctypes as C
+
+    import numpy as np
+
+    from . import capi
+    from .capi import check, lib
+
+    comm, _keep = capi.torch_host_comm(rank, world, group)
+    col = np.ascontiguousarray(colors, np.int32)
+    pl, ng, ptrs = C.c_void_p(), C.c_int32(), [C.c_void_p() for _ in range(7)]
+    check(lib.pmg_rowblock_plan_create(C.byref(comm), starts.ctypes.data, len(ci), ci.ctypes.data, 0, None, ncolors, col.ctypes.data, C.byref(pl)))
+    try:
+        check(lib.pmg_rowblock_plan_get(pl, C.byref(ng), *[C.byref(p_) for p_ in ptrs]))
+
+        def arr(k, n, ct):
+            return np.ctypeslib.as_array(C.cast(ptrs[k], C.POINTER(ct)), shape=(n,)).copy() if n else np.zeros(0, ct)
+
+        send_ptr = arr(1, ncolors + 1, C.c_int64)
+        plan = dict(send_ptr=send_ptr, send_rows=arr(2, int(send_ptr[-1]), C.c_int32), counts=arr(3, ncolors * world, C.c_int64).reshape(ncolors, world),
+                    recv_ptr=arr(4, ncolors + 1, C.c_int64), recv_src=arr(5, ng.value, C.c_int32), recv_rows=arr(6, ng.value, C.c_int32))
+        return arr(0, ng.value, C.c_int64), plan
+    finally:
+        lib.pmg_rowblock_plan_destroy(C.byref(pl))
+
+
+def _rbh_mgmc(comm, transport, levels, replicate_below: int, coloring: int = 0):
+    """The pmg_rbh_* call sequence of a hierarchy of MATMPIAIJ levels: levels[l] = dict(n=global rows, row0=, A=(rowptr,
+    colidx_global, vals) of this rank's rows, P=(rowptr, colidx_global_coarse, vals) of this rank's rows of P_l (l >= 1)),
+    level 0 = coarsest; the C side copies them.  Returns (rbh, mgmc): the pmg_mgmc handle borrows the hierarchy's arrays
+    until pmg_mgmc_setup, destroy rbh after it.  Collective over the ranks of `comm`."""
+    import ctypes as C
+
+    import numpy as np
+
+    from .capi import check, lib
+
+    rbh, mg = C.c_void_p(), C.c_void_p()
+    check(lib.pmg_rbh_create(C.byref(comm), len(levels), replicate_below, C.byref(rbh)))
+    try:
+        if coloring:  # 0: the library's default rule
+            check(lib.pmg_rbh_set_coloring(rbh, int(coloring)))
+        for l, Lv in enumerate(levels):
+            rp, ci, v = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(Lv["A"], (np.int64, np.int64, np.float64)))
+            check(lib.pmg_rbh_set_level_operator(rbh, l, Lv["n"], Lv["row0"], len(rp) - 1, rp.ctypes.data, ci.ctypes.data, v.ctypes.data, 64))
+            if l >= 1:
+                prp, pci, pv = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(Lv["P"], (np.int64, np.int64, np.float64)))
+                check(lib.pmg_rbh_set_level_interpolation(rbh, l, len(prp) - 1, prp.ctypes.data, pci.ctypes.data, pv.ctypes.data, 64))
+        check(lib.pmg_rbh_build(rbh))
+        check(lib.pmg_rbh_create_mgmc(rbh, transport, C.byref(mg)))
+    except Exception:
+        lib.pmg_rbh_destroy(C.byref(rbh))
+        raise
+    return rbh, mg
+
+
 class DistMCSOR:
     """mcgibbs / sorgibbs sampler for an assembled MATAIJ matrix distributed by ROW BLOCKS over `world` ranks
     (reference MCSORApply_MPIAIJ, src/mc_sor.c:298-381: for every colour, update the ghost values, then sweep the
@@ -487,12 +546,18 @@ class DistMCSOR:
         self.row0, self.row1, self.nloc, self.ncolors = row0, row1, row1 - row0, ncolors
         self.sweep_type, self.scaled = sweep_type, scaled
         rp = np.asarray(rowptr, np.int64)
-        ci = np.asarray(colidx, np.int64)
+        ci = np.ascontiguousarray(colidx, np.int64)
         v = np.asarray(vals, np.float64)
         assert len(rp) == self.nloc + 1 and len(colors) == self.nloc
-        is_ghost = (ci < row0) | (ci >= row1)
-        self.ghosts = np.unique(ci[is_ghost])  # sorted global ids of the ghost columns
+        # --- ghosts and scatter plan (pmg_rowblock.c): who owns my ghosts, what do the others need from me, in which colour
+        # does it change -- per colour one gather buffer, the ranks' blocks in rank order
+        ranges = [None] * world
+        dist.all_gather_object(ranges, (row0, row1), group=group)
+        starts = np.array([r[0] for r in ranges] + [n_global], np.int64)
+        self.ghosts, plan = _c_rowblock_plan(rank, world, group, starts, ci, colors, ncolors)  # sorted global ids of the ghost columns
+        self._plan = plan
         ng = len(self.ghosts)
+        is_ghost = (ci < row0) | (ci >= row1)
         loc = np.where(is_ghost, self.nloc + np.searchsorted(self.ghosts, ci), ci - row0)
         # local operator: my rows (entries in the order of the global CSR row) + one identity row per ghost column
         rp2 = np.concatenate([rp, rp[-1] + 1 + np.arange(ng)]).astype(np.int32)
@@ -506,34 +571,6 @@ class DistMCSOR:
         pos = self.mc.get_layout().astype(np.int64)
         self.ld = self.mc.layout_len()
         self.pos_local = torch.as_tensor(pos[: self.nloc], device="cuda")
-        # --- scatter plan: who owns my ghosts, what do the others need from me, in which colour does it change ---
-        ranges = [None] * world
-        dist.all_gather_object(ranges, (row0, row1), group=group)
-        starts = np.array([r[0] for r in ranges] + [n_global])
-        owner = np.searchsorted(starts, self.ghosts, side="right") - 1
-        want = [self.ghosts[owner == p] for p in range(world)]  # global rows I need from rank p
-        asked = [None] * world
-        dist.all_gather_object(asked, want, group=group)  # asked[q][p] = rows rank q needs from rank p
-        mycol = np.asarray(colors, np.int64)
-        reply = [mycol[np.asarray(asked[q][rank], np.int64) - row0] if q != rank else None for q in range(world)]
-        replies = [None] * world
-        dist.all_gather_object(replies, reply, group=group)  # replies[p][q] = colours of the rows q asked from p
-        self.send, self.recv = [], []  # per colour: list of (peer, positions in my layout vector)
-        for c in range(ncolors):
-            snd, rcv = [], []
-            for p in range(world):
-                if p == rank:
-                    continue
-                rows_p = np.asarray(asked[p][rank], np.int64)  # what p needs from me
-                sel = rows_p[mycol[rows_p - row0] == c] if len(rows_p) else rows_p
-                if len(sel):
-                    snd.append((p, torch.as_tensor(pos[sel - row0], device="cuda")))
-                g = want[p]
-                selg = g[np.asarray(replies[p][rank]) == c] if len(g) else g
-                if len(selg):
-                    rcv.append((p, torch.as_tensor(pos[self.nloc + np.searchsorted(self.ghosts, selg)], device="cuda")))
-            self.send.append(snd)
-            self.recv.append(rcv)
         self._staged = dist.get_backend(group) != "nccl"  # gloo: through host memory
         # --- the C driver (pmg_distmcsor.c): colour sweeps and ghost updates in one C loop on the stream, the updates as
         # one all-gather of the colour's boundary values over the "ipc" or "rccl" transport of pmg_dist.c.  transport
@@ -545,34 +582,35 @@ class DistMCSOR:
             drv, name = _agree_on_driver([want_tr] if want_tr else (["ipc", "rccl"] if on_gpu else []), lambda cand: IpcSlabDriver(None, rank, world, group=group) if cand == "ipc" else RcclSlabDriver(None, rank, world, group=group), rank, world, group, "row-block sampler")
             if drv is not None:
                 self._drv, self.transport = drv, name
+        send_ptr, counts, recv_ptr, recv_src = plan["send_ptr"], plan["counts"], plan["recv_ptr"], plan["recv_src"]
+        send_pos, recv_pos = pos[plan["send_rows"]], pos[plan["recv_rows"]]  # layout positions of the plan's local rows
+        # --- the point-to-point form of the same plan (exchange(); kept beside the C driver too): a ghost's index in the
+        # colour's gather buffer falls into its owner's block (prefix sums of counts[c]); its offset in that block is its
+        # index in the owner's send list of the colour.
+        # The plan lists ghosts per colour and owner by ascending global row: the order the messages carry.
+        offs = np.concatenate([np.zeros((ncolors, 1), np.int64), np.cumsum(counts, axis=1)], axis=1)
+        self.send, self.recv = [], []  # per colour: list of (peer, positions in my layout vector)
+        reads = [[None] * ncolors for _ in range(world)]  # reads[p][c] = the indices of p's colour-c send list I read
+        for c in range(ncolors):
+            sl = slice(recv_ptr[c], recv_ptr[c + 1])
+            src = recv_src[sl].astype(np.int64)
+            peer = np.searchsorted(offs[c], src, side="right") - 1
+            self.recv.append([(p, torch.as_tensor(recv_pos[sl][peer == p], device="cuda")) for p in range(world) if (peer == p).any()])
+            for p in range(world):
+                reads[p][c] = src[peer == p] - offs[c, p]
+        wanted = [None] * world
+        dist.all_gather_object(wanted, reads, group=group)  # wanted[q][rank][c] = what rank q reads of my colour-c send list
+        for c in range(ncolors):
+            mine = send_pos[send_ptr[c]:send_ptr[c + 1]]
+            self.send.append([(q, torch.as_tensor(mine[wanted[q][rank][c]], device="cuda")) for q in range(world) if q != rank and len(wanted[q][rank][c])])
         if self._drv is not None:
             import ctypes as C
 
             from .capi import check, lib
 
-            others = [np.asarray(asked[p][rank], np.int64) for p in range(world) if p != rank]
-            needed = np.unique(np.concatenate(others)) if others else np.zeros(0, np.int64)  # my rows that another rank reads
-            send_lists = [needed[mycol[needed - row0] == c] for c in range(ncolors)]  # sorted global rows, by colour
-            all_lists = [None] * world
-            dist.all_gather_object(all_lists, send_lists, group=group)
-            counts = np.array([[len(all_lists[r][c]) for r in range(world)] for c in range(ncolors)], np.int64)
-            offs = np.concatenate([np.zeros((ncolors, 1), np.int64), np.cumsum(counts, axis=1)[:, :-1]], axis=1)
-            send_ptr = np.concatenate([[0], np.cumsum([len(l) for l in send_lists])]).astype(np.int64)
-            send_pos = (np.concatenate([pos[l - row0] for l in send_lists]) if send_ptr[-1] else np.zeros(0)).astype(np.int32)
-            gid = np.concatenate([want[p] for p in range(world)]) if ng else np.zeros(0, np.int64)  # my ghosts, by owner
-            gown = np.concatenate([np.full(len(want[p]), p) for p in range(world)]) if ng else np.zeros(0, np.int64)
-            gcol = np.concatenate([np.asarray(replies[p][rank] if p != rank else [], np.int64) for p in range(world)]) if ng else np.zeros(0, np.int64)
-            rsrc, rpos, rptr = [], [], [0]
-            for c in range(ncolors):
-                sel = np.nonzero(gcol == c)[0]
-                for q in sel:
-                    pown = int(gown[q])
-                    rsrc.append(int(offs[c, pown] + np.searchsorted(all_lists[pown][c], gid[q])))
-                    rpos.append(int(pos[self.nloc + np.searchsorted(self.ghosts, gid[q])]))
-                rptr.append(len(rsrc))
-            recv_ptr, recv_src, recv_pos = np.asarray(rptr, np.int64), np.asarray(rsrc, np.int32), np.asarray(rpos, np.int32)
+            send_pos, recv_pos = send_pos.astype(np.int32), recv_pos.astype(np.int32)
             self._c = C.c_void_p()
-            check(lib.pmg_distmcsor_create(self.mc._h, self._drv._h, ncolors, send_ptr.ctypes.data, send_pos.ctypes.data, np.ascontiguousarray(counts).ctypes.data, recv_ptr.ctypes.data, recv_src.ctypes.data, recv_pos.ctypes.data, C.byref(self._c)))
+            check(lib.pmg_distmcsor_create(self.mc._h, self._drv._h, ncolors, send_ptr.ctypes.data, send_pos.ctypes.data, counts.ctypes.data, recv_ptr.ctypes.data, recv_src.ctypes.data, recv_pos.ctypes.data, C.byref(self._c)))
 
     def set_lowrank(self, B_owned, S):
         """MATLRC operator A + B diag(S) B^T (reference MCSORSetUp's LRC branch, src/mc_sor.c:572-595): B_owned = this
@@ -666,128 +704,6 @@ class DistMCSOR:
             pass
 
 
-def rowblock_plan(ci_global, row0: int, row1: int, n_global: int, colors_owned, ncolors: int, extra_ghosts, rank: int, world: int, group=None):
-    """Ghost set and per-colour ghost-update plan of one row block (what MatCreateScatters builds per colour in the
-    reference, src/mc_sor.c:152-214; here de-duplicated per ghost row and laid out for ONE all-gather per colour).
-
-    ci_global: the global column indices of this rank's rows; extra_ghosts: further global rows of other ranks whose
-    values this rank reads (restriction / interpolation columns).  Returns (ghosts, plan) with ghosts = sorted global
-    ids (local row nloc + q) and plan = dict(send_ptr, send_rows, counts, recv_ptr, recv_src, recv_rows): local OWNED rows
-    this rank contributes per colour (by ascending global row), the ranks' block lengths, and for every ghost row the
-    index of its value in the colour's gather buffer (blocks in rank order).  Collective over `group` (host objects)."""
-    import numpy as np
-    import torch.distributed as dist
-
-    ci = np.asarray(ci_global, np.int64)
-    nloc = row1 - row0
-    off = ci[(ci < row0) | (ci >= row1)]
-    extra = np.asarray(extra_ghosts, np.int64)
-    extra = extra[(extra < row0) | (extra >= row1)]
-    ghosts = np.unique(np.concatenate([off, extra]))
-    ranges = [None] * world
-    dist.all_gather_object(ranges, (row0, row1), group=group)
-    starts = np.array([r[0] for r in ranges] + [n_global])
-    assert all(ranges[r][1] == starts[r + 1] for r in range(world)), "row blocks must tile the rows in rank order"
-    owner = np.searchsorted(starts, ghosts, side="right") - 1
-    want = [ghosts[owner == p] for p in range(world)]  # global rows I need from rank p
-    asked = [None] * world
-    dist.all_gather_object(asked, want, group=group)  # asked[q][p] = rows rank q needs from rank p
-    mycol = np.asarray(colors_owned, np.int64)
-    assert len(mycol) == nloc and (nloc == 0 or (mycol.min() >= 0 and mycol.max() < ncolors))
-    others = [np.asarray(asked[q][rank], np.int64) for q in range(world) if q != rank]
-    needed = np.unique(np.concatenate(others)) if others else np.zeros(0, np.int64)  # my rows that another rank reads
-    send_lists = [needed[mycol[needed - row0] == c] for c in range(ncolors)]  # sorted global rows, by colour
-    all_lists = [None] * world
-    dist.all_gather_object(all_lists, send_lists, group=group)
-    counts = np.array([[len(all_lists[r][c]) for r in range(world)] for c in range(ncolors)], np.int64).reshape(ncolors, world)
-    offs = np.concatenate([np.zeros((ncolors, 1), np.int64), np.cumsum(counts, axis=1)[:, :-1]], axis=1)
-    send_ptr = np.concatenate([[0], np.cumsum([len(l) for l in send_lists])]).astype(np.int64)
-    send_rows = (np.concatenate(send_lists) - row0 if send_ptr[-1] else np.zeros(0)).astype(np.int32)
-    rsrc, rrow, rptr = [], [], [0]
-    for c in range(ncolors):
-        for p in range(world):
-            if p == rank or not len(want[p]):
-                continue
-            lst = np.asarray(all_lists[p][c], np.int64)
-            if not len(lst):
-                continue
-            k = np.searchsorted(lst, want[p])
-            hit = (k < len(lst)) & (lst[np.minimum(k, len(lst) - 1)] == want[p])  # my ghosts owned by p that have colour c
-            rsrc.append(offs[c, p] + k[hit])
-            rrow.append(nloc + np.searchsorted(ghosts, want[p][hit]))
-        rptr.append(sum(len(a) for a in rsrc))
-    plan = dict(send_ptr=send_ptr, send_rows=send_rows, counts=np.ascontiguousarray(counts),
-                recv_ptr=np.asarray(rptr, np.int64),
-                recv_src=(np.concatenate(rsrc) if rsrc else np.zeros(0)).astype(np.int32),
-                recv_rows=(np.concatenate(rrow) if rrow else np.zeros(0)).astype(np.int32))
-    assert plan["recv_ptr"][-1] == len(ghosts), "every ghost row is owned by exactly one rank and has exactly one colour"
-    return ghosts, plan
-
-
-def rowblock_hierarchy(operators, interpolations, colorings, rank: int, world: int, starts=None, replicate_below: int = 50000, group=None):
-    """This rank's share of a hierarchy distributed by row blocks -- host arrays only, no device, no C call; collective
-    (the ghost plans of rowblock_plan).  operators / interpolations as for MGMC.from_hierarchy (level 0 = coarsest),
-    colorings[l] = (colours of ALL rows of level l, number of colours) for the levels that will be row blocks (None below).
-    Returns dict(fold, starts, n, levels): levels[l] for l >= fold holds the local operator (rp, ci, v: owned rows in
-    global order, entries in global CSR order, then one identity row per ghost), colors (owned rows), ncolors, plan,
-    ghosts (sorted global rows), nowned, row0, P (owned rows of P_l, columns in the local numbering of level l-1 -- global
-    when that level is replicated) and R (the rows of P_l^T this rank owns on level l-1, columns in the local numbering of
-    level l, entries by ascending global fine row).  Levels below `fold` are replicated (levels[l] = None)."""
-    import numpy as np
-    import scipy.sparse as sp
-
-    L = len(operators)
-    assert L >= 2 and len(interpolations) == L
-    A = [sp.csr_matrix((np.asarray(v, np.float64), np.asarray(ci, np.int64), np.asarray(rp, np.int64)), shape=(len(rp) - 1, len(rp) - 1)) for rp, ci, v in operators]
-    P = [None] + [sp.csr_matrix((np.asarray(interpolations[l][2], np.float64), np.asarray(interpolations[l][1], np.int64), np.asarray(interpolations[l][0], np.int64)), shape=(A[l].shape[0], A[l - 1].shape[0])) for l in range(1, L)]
-    n = [a.shape[0] for a in A]
-    if starts is None:
-        starts = [np.linspace(0, n[l], world + 1).astype(np.int64) for l in range(L)]
-    starts = [np.asarray(s_, np.int64) for s_ in starts]
-    r0 = [int(s_[rank]) for s_ in starts]
-    r1 = [int(s_[rank + 1]) for s_ in starts]
-    R = [None] + [P[l].T.tocsr() for l in range(1, L)]  # rows of P^T, entries by ascending fine row
-    for m in R[1:]:
-        m.sort_indices()
-    fold = 1  # lowest row-block level; the levels below are replicated
-    while fold < L - 1 and n[fold] <= replicate_below:
-        fold += 1
-    ghosts, nloc = [np.zeros(0, np.int64)] * L, [r1[l] - r0[l] for l in range(L)]
-    local_of = [None] * L  # global row -> local row of this rank (owned, then ghosts), -1 elsewhere; replicated levels: identity
-    for l in range(fold):
-        local_of[l] = np.arange(n[l], dtype=np.int64)
-    levels = [None] * L
-    for l in range(fold, L):
-        col, ncol = colorings[l]
-        col = np.asarray(col)
-        mine = A[l][r0[l]:r1[l]]
-        extra = [R[l][r0[l - 1]:r1[l - 1]].indices.astype(np.int64)]  # fine rows my restriction rows read (level l-1 replicated: the block I restrict into)
-        if l + 1 < L:
-            extra.append(P[l + 1][r0[l + 1]:r1[l + 1]].indices.astype(np.int64))  # rows of this level the finer level's interpolation reads
-        ghosts[l], plan = rowblock_plan(mine.indices, r0[l], r1[l], n[l], col[r0[l]:r1[l]], ncol, np.concatenate(extra), rank, world, group)
-        ng = len(ghosts[l])
-        lo = np.full(n[l], -1, np.int64)
-        lo[r0[l]:r1[l]] = np.arange(nloc[l])
-        lo[ghosts[l]] = nloc[l] + np.arange(ng)
-        local_of[l] = lo
-        # local operator: my rows (entries in the order of the global CSR row) + one identity row per ghost
-        rp = np.concatenate([mine.indptr, mine.indptr[-1] + 1 + np.arange(ng)]).astype(np.int32)
-        ci = np.concatenate([lo[mine.indices], nloc[l] + np.arange(ng)]).astype(np.int32)
-        assert ci.min(initial=0) >= 0
-        v = np.concatenate([mine.data, np.ones(ng)])
-        levels[l] = dict(rp=rp, ci=ci, v=v, colors=np.ascontiguousarray(col[r0[l]:r1[l]], np.int32), ncolors=int(ncol), plan=plan, ghosts=ghosts[l], nowned=nloc[l], row0=r0[l])
-    for l in range(fold, L):
-        pm = P[l][r0[l]:r1[l]]  # my rows of P_l (entries in the caller's order), columns -> local numbering of level l-1
-        prp, pci, pv = pm.indptr.astype(np.int32), local_of[l - 1][pm.indices].astype(np.int32), np.ascontiguousarray(pm.data)
-        rm = R[l][r0[l - 1]:r1[l - 1]]  # the rows of P_l^T I own on level l-1, columns -> local numbering of level l
-        rrp, rci, rv = rm.indptr.astype(np.int32), local_of[l][rm.indices].astype(np.int32), np.ascontiguousarray(rm.data)
-        assert pci.min(initial=0) >= 0 and rci.min(initial=0) >= 0, "a transfer reads a row that is neither owned nor a ghost"
-        levels[l]["P"] = (prp, pci, pv)
-        levels[l]["R"] = (rrp, rci, rv)
-        levels[l]["ncoarse_local"] = n[l - 1] if l == fold else nloc[l - 1] + len(ghosts[l - 1])
-    return dict(fold=fold, starts=starts, n=n, levels=levels)
-
-
 class DistAIJMGMC:
     """MGMC sampler on a caller-supplied hierarchy of assembled MATAIJ matrices distributed by ROW BLOCKS, one rank per
     device: the reference's PCGAMGMC on a MATMPIAIJ (src/pc_gamgmc.c:157-223; level sampler MCSORApply_MPIAIJ,
@@ -799,74 +715,49 @@ class DistAIJMGMC:
     which is factored redundantly: there every rank runs the single-device kernels on identical data, which costs less
     than a ghost update per colour for a few thousand rows.  The whole sample loop -- colour
     sweeps, ghost updates, residuals, transfers, coarse solve -- runs in C (pmg_mgmc.c) on the stream; this class only
-    slices the matrices and builds the ghost plans (host set-up, collective).  Bit-identical to MGMC.from_hierarchy."""
+    slices the matrices, the set-up is pmg_rowblock.c's (pmg_rbh_*; host code, collective) -- the one the adapter reaches
+    through CRowBlock's route.  Bit-identical to MGMC.from_hierarchy."""
 
     def __init__(self, operators, interpolations, rank: int, world: int, group=None, transport=None, starts=None, replicate_below: int = 50000, coloring: int = 0):
         import ctypes as C
         import os
 
         import numpy as np
-        import scipy.sparse as sp
-        import torch
-        import torch.distributed as dist
 
-        from .capi import check, lib
-        from .wrappers import MCSOR
+        from . import capi
+        from .capi import RbhLevelView, check, lib
 
         self.rank, self.world, self.group = rank, world, group
         L = len(operators)
         assert L >= 2 and len(interpolations) == L
         n = [len(op[0]) - 1 for op in operators]
         # --- transport: the generic all-gather of pmg_dist.c ("ipc" peer stores or RCCL), agreed between the ranks
-        on_gpu = dist.get_backend(group) == "nccl"
         want_tr = transport or os.environ.get("PMG_DIST_TRANSPORT")
         self._drv, self.transport = _agree_on_driver([want_tr] if want_tr else ["ipc", "rccl"], lambda cand: IpcSlabDriver(None, rank, world, group=group) if cand == "ipc" else RcclSlabDriver(None, rank, world, group=group), rank, world, group, "row-block hierarchy")
         if self._drv is None:
             raise RuntimeError("DistAIJMGMC needs the 'ipc' or 'rccl' transport of the HIP library")
-        # --- the global colouring of the row-block levels: the library's first-fit rule, as MGMC.from_hierarchy applies it
-        fold = 1
-        while fold < L - 1 and n[fold] <= replicate_below:
-            fold += 1
-        colorings = [None] * L
-        for l in range(fold, L):
-            rp, ci, v = operators[l]
-            mc = MCSOR(np.ascontiguousarray(rp, np.int32), np.ascontiguousarray(ci, np.int32), np.ascontiguousarray(v, np.float64), coloring).setup()  # capi.COLORING_GREEDY (0) or COLORING_ITERATED: what MGMC.from_hierarchy + set_coloring(rule) sweeps with on one device
-            colorings[l] = (mc.get_coloring(), mc.get_num_colors())
-            mc.destroy()
-        H = rowblock_hierarchy(operators, interpolations, colorings, rank, world, starts=starts, replicate_below=replicate_below, group=group)
-        assert H["fold"] == fold
-        self.fold, self.starts = fold, H["starts"]
-        # --- hand everything to the C hierarchy
-        self._keep = [H]
-        self._h = C.c_void_p()
-        check(lib.pmg_mgmc_create_hierarchy(L, C.byref(self._h)))
-        check(lib.pmg_mgmc_set_coloring(self._h, int(coloring)))  # the replicated AIJ levels below the fold
-        a0 = sp.csr_matrix((np.asarray(operators[0][2], np.float64), np.asarray(operators[0][1], np.int64), np.asarray(operators[0][0], np.int64)), shape=(n[0], n[0]))
-        a0.sort_indices()
-        rp0, ci0, v0 = a0.indptr.astype(np.int32), a0.indices.astype(np.int32), np.ascontiguousarray(a0.data)
-        self._keep.append((rp0, ci0, v0))
-        check(lib.pmg_mgmc_set_level_operator(self._h, 0, n[0], rp0.ctypes.data, ci0.ctypes.data, v0.ctypes.data))
-        cs = np.ascontiguousarray(self.starts[fold - 1], np.int64)  # who restricts which rows of the highest replicated level
-        self._keep.append(cs)
-        check(lib.pmg_mgmc_set_rowblock_transport(self._h, self._drv._h, cs.ctypes.data))
-        for l in range(1, fold):  # replicated level: the whole operator and interpolation, as MGMC.from_hierarchy takes them
-            rp, ci, v = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(operators[l], (np.int32, np.int32, np.float64)))
-            prp, pci, pv = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(interpolations[l], (np.int32, np.int32, np.float64)))
-            self._keep += [rp, ci, v, prp, pci, pv]
-            check(lib.pmg_mgmc_set_level_operator(self._h, l, n[l], rp.ctypes.data, ci.ctypes.data, v.ctypes.data))
-            check(lib.pmg_mgmc_set_level_interpolation(self._h, l, n[l], n[l - 1], prp.ctypes.data, pci.ctypes.data, pv.ctypes.data))
-        for l in range(fold, L):
-            Lv = H["levels"][l]
-            plan, nl = Lv["plan"], Lv["nowned"] + len(Lv["ghosts"])
-            check(lib.pmg_mgmc_set_level_operator(self._h, l, nl, Lv["rp"].ctypes.data, Lv["ci"].ctypes.data, Lv["v"].ctypes.data))
-            check(lib.pmg_mgmc_set_level_rowblock(self._h, l, Lv["row0"], Lv["nowned"], Lv["ncolors"], Lv["colors"].ctypes.data, plan["send_ptr"].ctypes.data, plan["send_rows"].ctypes.data, plan["counts"].ctypes.data,
-                                                  plan["recv_ptr"].ctypes.data, plan["recv_src"].ctypes.data, plan["recv_rows"].ctypes.data))
-            (prp, pci, pv), (rrp, rci, rv) = Lv["P"], Lv["R"]
-            check(lib.pmg_mgmc_set_level_interpolation(self._h, l, Lv["nowned"], Lv["ncoarse_local"], prp.ctypes.data, pci.ctypes.data, pv.ctypes.data))
-            check(lib.pmg_mgmc_set_level_restriction(self._h, l, len(rrp) - 1, nl, rrp.ctypes.data, rci.ctypes.data, rv.ctypes.data))
-        top = H["levels"][L - 1]
-        self.n_owned, self.n_local = top["nowned"], top["nowned"] + len(top["ghosts"])
-        self.row_range = (top["row0"], top["row0"] + top["nowned"])
+        # --- this rank's rows of every level, global columns, entries in the caller's order (the summation order of a row);
+        # fold, colouring (the rule MGMC.from_hierarchy + set_coloring(rule) sweeps with on one device), restriction rows,
+        # ghost plans and local matrices are pmg_rowblock.c's
+        if starts is None:
+            starts = [np.linspace(0, n[l], world + 1).astype(np.int64) for l in range(L)]
+
+        def rows(triple, r0, r1):
+            rp, ci, v = (np.asarray(a_) for a_ in triple)
+            return rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], v[rp[r0]:rp[r1]]
+
+        cut = [(int(starts[l][rank]), int(starts[l][rank + 1])) for l in range(L)]
+        self._comm = capi.torch_host_comm(rank, world, group)  # (pmg_host_comm, its callback): alive while the C side may call back
+        self._h = None
+        self._rbh, self._h = _rbh_mgmc(self._comm[0], self._drv._h, [dict(n=n[l], row0=cut[l][0], A=rows(operators[l], *cut[l]), P=rows(interpolations[l], *cut[l]) if l >= 1 else None) for l in range(L)], replicate_below, coloring)
+        fold, views = C.c_int32(), [RbhLevelView() for _ in range(L)]
+        check(lib.pmg_rbh_get_info(self._rbh, None, C.byref(fold)))
+        for l in range(L):
+            check(lib.pmg_rbh_get_level(self._rbh, l, C.byref(views[l])))
+        self.fold, self.starts = fold.value, [np.ctypeslib.as_array(v_.starts, shape=(world + 1,)).copy() for v_ in views]
+        top = views[L - 1]
+        self.n_owned, self.n_local = top.nowned, top.nlocal
+        self.row_range = (top.row0, top.row0 + top.nowned)
         self.levels = L
 
     def set_smoother(self, scaled: bool, omega: float = 1.0, sweep_type: int = SOR_FORWARD_SWEEP, its: int = 1):
@@ -906,6 +797,8 @@ class DistAIJMGMC:
         check(lib.pmg_mgmc_set_lowrank(self._h, len(S), Bl.ctypes.data, S.ctypes.data))
 
     def setup(self):
+        import ctypes as C
+
         from .capi import check, lib
 
         err = None
@@ -914,6 +807,7 @@ class DistAIJMGMC:
         except Exception as e:  # noqa: BLE001
             err = e
         _all_ok(err, self.group, "row-block hierarchy set-up")
+        lib.pmg_rbh_destroy(C.byref(self._rbh))  # the arrays were borrowed until set-up
         return self
 
     def sample(self, b_owned, y_owned, its: int, seed: int, counter0: int = 0, guesszero: bool = False) -> int:
@@ -942,6 +836,8 @@ class DistAIJMGMC:
         if getattr(self, "_h", None) is not None and self._h:
             lib.pmg_mgmc_destroy(C.byref(self._h))
             self._h = None
+        if getattr(self, "_rbh", None):  # no set-up ran
+            lib.pmg_rbh_destroy(C.byref(self._rbh))
         if getattr(self, "_drv", None) is not None:
             self._drv.destroy()  # collective: disconnect, barrier, destroy
             self._drv = None
@@ -951,7 +847,9 @@ class CRowBlock:
     """The multi-rank samplers on MATMPIAIJ row blocks reached through the C-ABI ALONE (pmg_rowblock.c): transport bootstrap,
     colouring, ghost plans, local operators and the sample loops are C; Python only supplies the byte all-gather callback
     (torch.distributed here, MPI_Allgather in adapter/, pipes in examples/pmg_bench.c) and device tensors.  This is what a
-    PETSc caller with an MPI_Comm uses; DistMCSOR / DistAIJMGMC above are the round-2 Python builders the C plans are pinned to.
+    PETSc caller with an MPI_Comm uses.  DistMCSOR / DistAIJMGMC above take the same ghost plans and the same hierarchy from
+    pmg_rowblock.c (DistAIJMGMC through the call sequence of `mgmc` below); they differ in who slices the rows (they do, from
+    global matrices every rank holds) and who makes the transport (IpcSlabDriver / RcclSlabDriver over torch.distributed).
 
       CRowBlock.sampler(...)  MCSORCreate + MCSORSetUp + the sample loop on a MATMPIAIJ (reference src/mc_sor.c:298-381,553-605)
       CRowBlock.mgmc(...)     PCGAMGMC on a hierarchy of MATMPIAIJ levels (src/pc_gamgmc.c:157-264)"""
@@ -1029,18 +927,7 @@ class CRowBlock:
         from .capi import RbhLevelView, check, lib
 
         L = len(levels)
-        check(lib.pmg_rbh_create(C.byref(self.comm), L, replicate_below, C.byref(self._rbh)))
-        keep = []
-        for l, Lv in enumerate(levels):
-            rp, ci, v = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(Lv["A"], (np.int64, np.int64, np.float64)))
-            keep += [rp, ci, v]
-            check(lib.pmg_rbh_set_level_operator(self._rbh, l, Lv["n"], Lv["row0"], len(rp) - 1, rp.ctypes.data, ci.ctypes.data, v.ctypes.data, 64))
-            if l >= 1:
-                prp, pci, pv = (np.ascontiguousarray(a_, t_) for a_, t_ in zip(Lv["P"], (np.int64, np.int64, np.float64)))
-                keep += [prp, pci, pv]
-                check(lib.pmg_rbh_set_level_interpolation(self._rbh, l, len(prp) - 1, prp.ctypes.data, pci.ctypes.data, pv.ctypes.data, 64))
-        check(lib.pmg_rbh_build(self._rbh))
-        check(lib.pmg_rbh_create_mgmc(self._rbh, self._dist, C.byref(self._mg)))
+        self._rbh, self._mg = _rbh_mgmc(self.comm, self._dist, levels, replicate_below)
         check(lib.pmg_mgmc_set_smoother(self._mg, int(smoother[0]), smoother[1], smoother[2], smoother[3]))
         view = RbhLevelView()
         check(lib.pmg_rbh_get_level(self._rbh, L - 1, C.byref(view)))

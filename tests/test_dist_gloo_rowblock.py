@@ -1,4 +1,4 @@
-"""world_size 2 / 3 `gloo` test (CPU) of the ghost-update plan of a row-block distributed level (parmgmc_amd.dist.
+"""world_size 2 / 3 `gloo` test (CPU) of the ghost-update plan of a row-block distributed level (tests/rowblock_reference.py,
 rowblock_plan: what MatCreateScatters builds per colour in the reference, src/mc_sor.c:152-214): executed with numpy
 exactly as pmg_distmcsor.c executes it -- per colour: gather the send rows, concatenate the ranks' blocks in rank order,
 scatter recv_src -> recv_rows -- every ghost row must end up with its owner's value, for the operator's own off-process
@@ -35,7 +35,7 @@ def _worker(rank, world, port, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    from parmgmc_amd.dist import rowblock_plan
+    from rowblock_reference import rowblock_plan
 
     A, col, extra = _problem()
     n = A.n
@@ -79,7 +79,7 @@ def test_rowblock_plan_delivers_every_ghost_row(world):
     assert all(r[1] and r[2] and r[3] for r in res), res
 
 
-# ---- the row-block V-cycle as an algorithm (host logic of parmgmc_amd.dist.rowblock_hierarchy) ------------------------------
+# ---- the row-block V-cycle as an algorithm (host logic of rowblock_reference.rowblock_hierarchy) ------------------------------
 # numpy restatement of what pmg_mgmc.c does with the arrays rowblock_hierarchy hands it -- per-colour Gauss-Seidel sweeps with a
 # ghost update after every colour, residual on the owned rows, ghost refresh of the residual, the owned rows of P^T, the
 # all-gather into the replicated levels, the replicated levels as on one device, exact coarse solve, the owned rows of P --
@@ -113,7 +113,7 @@ def _vcycle_worker(rank, world, port, replicate_below, q):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
-    from parmgmc_amd.dist import rowblock_hierarchy
+    from rowblock_reference import rowblock_hierarchy
 
     ops, ps = _hier()
     L = len(ops)

@@ -312,6 +312,12 @@ def _csr_worker(rank, world, port, which, omega, sweep_type, its, q, transport=N
     sl = slice(A.rowptr[r0], A.rowptr[r1])
     smp = DistMCSOR(rp, A.colidx[sl], A.vals[sl], r0, r1, n, colors[r0:r1], int(colors.max()) + 1, rank, world, omega=omega, sweep_type=sweep_type, transport=transport)
     assert smp.transport == (transport or "torch") and (smp._c is not None) == (transport == "ipc")
+    if smp._c is None:  # the per-peer lists derived from the C plan cover every ghost of a colour exactly once
+        pos, plan = smp.mc.get_layout().astype(np.int64), smp._plan
+        for c in range(smp.ncolors):
+            got = np.concatenate([idx.cpu().numpy() for _, idx in smp.recv[c]] + [np.zeros(0, np.int64)])
+            want = pos[plan["recv_rows"][plan["recv_ptr"][c]:plan["recv_ptr"][c + 1]]]
+            assert len(set(got.tolist())) == len(got) and set(got.tolist()) == set(want.tolist())
     if lowrank:
         B, S = _csr_lowrank_factors(n, lowrank_k)
         smp.set_lowrank(B[r0:r1], S)
@@ -400,7 +406,13 @@ def _aij_mg_worker(rank, world, port, refine, coarse_max, opts, its, q):
     from parmgmc_amd.dist import DistAIJMGMC
 
     ops, ps = _aij_hierarchy(refine, coarse_max)
-    mg = DistAIJMGMC(ops, ps, rank, world, transport="ipc", replicate_below=opts["replicate_below"], coloring=opts.get("coloring", 0))
+    starts = None
+    if opts.get("starts_cut"):  # the caller's uneven row blocks: two ranks, every level cut at the same fraction of its rows
+        starts = [np.array([0, int(opts["starts_cut"] * (len(op[0]) - 1)), len(op[0]) - 1], np.int64) for op in ops]
+    mg = DistAIJMGMC(ops, ps, rank, world, transport="ipc", replicate_below=opts["replicate_below"], coloring=opts.get("coloring", 0), starts=starts)
+    if starts is not None:
+        assert mg.row_range == (starts[-1][rank], starts[-1][rank + 1]) and mg.n_owned == starts[-1][rank + 1] - starts[-1][rank]
+        assert all(np.array_equal(a, b) for a, b in zip(mg.starts, starts))
     mg.set_smoother(opts["scaled"], opts["omega"], opts["sweep"], opts["nu"])
     mg.set_correction_form(opts["literal"])
     n = len(ops[-1][0]) - 1
@@ -435,7 +447,8 @@ def _aij_mg_worker(rank, world, port, refine, coarse_max, opts, its, q):
     (3, 300, 2, {"replicate_below": 500, "lowrank": True, "scaled": True}),                  # the low-rank block is handed to the replicated levels at the fold
     (2, 300, 2, {"replicate_below": 10 ** 9}),                                                # only the finest level by row blocks
     (3, 300, 2, {"replicate_below": 2000, "scaled": True, "coloring": 3}),                   # PMG_COLORING_ITERATED on row-block and replicated levels (round 4)
-], ids=["1rank", "2ranks", "3ranks_symmetric_nu2", "4ranks_backward_4levels", "2ranks_literal", "3ranks_lowrank", "2ranks_lowrank_literal", "3ranks_lowrank_k64", "3ranks_replicated_small_levels", "2ranks_replicated_lowrank", "2ranks_only_finest_distributed", "2ranks_iterated_colouring"])
+    (2, 300, 2, {"starts_cut": 0.37}),                                                        # the caller's uneven row blocks: 37 % / 63 % of every level
+], ids=["1rank", "2ranks", "3ranks_symmetric_nu2", "4ranks_backward_4levels", "2ranks_literal", "3ranks_lowrank", "2ranks_lowrank_literal", "3ranks_lowrank_k64", "3ranks_replicated_small_levels", "2ranks_replicated_lowrank", "2ranks_only_finest_distributed", "2ranks_iterated_colouring", "2ranks_uneven_starts"])
 def test_row_block_distributed_aij_vcycle_reproduces_the_single_device_chain(refine, coarse_max, world, opts):
     """PCGAMGMC on a MATMPIAIJ hierarchy (reference src/pc_gamgmc.c:157-223 over MCSORApply_MPIAIJ, src/mc_sor.c:298-381):
     the aggregation hierarchy of the P1 matrix of the reference's lshape.msh, every level above the coarsest split into

@@ -1,5 +1,5 @@
-"""The row-block set-up in C (parmgmc_amd/csrc/pmg_rowblock.c) against the Python builders of round 2
-(parmgmc_amd/dist.py: rowblock_plan, rowblock_hierarchy), index for index, under `gloo` with 1, 2 and 3 ranks on the CPU --
+"""The row-block set-up in C (parmgmc_amd/csrc/pmg_rowblock.c) against the tests' numpy / scipy reference
+(tests/rowblock_reference.py: rowblock_plan, rowblock_hierarchy), index for index, under `gloo` with 1, 2 and 3 ranks on the CPU --
 no GPU: the plan builders are host code.  The C side sees ONLY what a PETSc caller holds (MatMPIAIJGetSeqAIJ's diagonal and
 off-diagonal blocks + garray, MatGetOwnershipRanges, reference src/mc_sor.c:152-214,308) and one byte all-gather callback
 (here torch.distributed; MPI_Allgather in adapter/).  Also: the merge of the two blocks, and the distributed first-fit
@@ -60,7 +60,7 @@ def _worker(rank, world, port, idx_width, q):
 
     from parmgmc_amd import capi
     from parmgmc_amd.capi import check, lib
-    from parmgmc_amd.dist import rowblock_hierarchy
+    from rowblock_reference import rowblock_hierarchy
 
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
