@@ -5,10 +5,19 @@ Replaces the reference's MPI design -- row-block ownership of a MATMPIAIJ with o
 
 * ``DistGridSampler`` -- sorgibbs / mcgibbs on the DMDA operator, z-slabs (`slab_cuts`, PETSc's ownership rule).  The
   sample loop is the C loop of pmg_dist.c over the "ipc" transport (peer stores + flag words, hand-shake inside the
-  sweep kernel) or RCCL send/recv (``IpcSlabDriver`` / ``RcclSlabDriver``); ``run_samples`` + ``SlabHalo`` is the same
+  sweep kernel) or RCCL send/recv (``SlabDriver``); ``run_samples`` + ``SlabHalo`` is the same
   schedule over torch.distributed point-to-point ops (RCCL tensors, or gloo through host memory in the CPU tests).
 * ``DistMGMC`` -- the Multigrid Monte Carlo V-cycle on z-slabs (pmg_mgmc_create_dmda_slab), incl. low-rank updates.
 * ``DistMCSOR`` -- general MATAIJ matrices by row blocks: per-colour device sweeps, ghost updates between them.
+* ``DistAIJMGMC`` / ``CRowBlock`` -- MGMC on a hierarchy of MATAIJ levels by row blocks (``_RowBlockMGMC``).
+
+One bootstrap: every class gets its "ipc" or "rccl" transport from ``SlabDriver``, that is from pmg_dist_create_comm of
+pmg_rowblock.c over a byte all-gather on torch.distributed -- the call the adapter makes over MPI_Allgather; the
+agreements after each step that can fail on one rank alone, and the tear-down of a half-built transport, are the
+library's.  Python adds two things.  ``_agree_on_driver`` falls back from one transport to the next (ipc -> rccl ->
+torch P2P) after the driver's ``selftest()``, a local round trip that can fail on one rank alone.  ``_teardown`` is the one
+tear-down order (disconnect, device synchronise, barrier, free); it is Python, not pmg_dist_destroy_comm, because after a
+failed agreement a rank WITHOUT an object must join it, and such a rank can only be met through torch.distributed.
 
 Because noise is a function of global indices only, every chain is the single-device chain for any number of ranks.
 torch is plumbing here: the sweeps are the HIP kernels behind the C-ABI.
@@ -118,7 +127,9 @@ def _teardown(drv, world: int, group) -> None:
     """Orderly end of a transport, COLLECTIVE over all ranks of `group` -- entered by every rank whether or not it holds
     a driver (drv None: its constructor failed on this rank alone): unmap the peers' blocks, barrier, free the own block.
     A rank that frees a block a peer still has mapped and exports a fresh one at once gets "invalid argument" from
-    hipIpcGetMemHandle; a rank that skipped the barrier would meet its peers in a different collective."""
+    hipIpcGetMemHandle; a rank that skipped the barrier would meet its peers in a different collective.  This stays Python
+    (pmg_dist_destroy_comm is the adapter's): falling back from one transport to the next needs a tear-down that a rank
+    without an object can join, and such a rank has only torch.distributed to join it through."""
     if drv is not None and getattr(drv, "_h", None):
         drv.disconnect()
     if world > 1:
@@ -134,7 +145,8 @@ def _teardown(drv, world: int, group) -> None:
 
 def _agree_on_driver(candidates, make, rank: int, world: int, group, what: str):
     """Try the transports in order; every rank must end up on the same one.  make(name) builds a driver (collective
-    internally; may fail on one rank alone, by raising or by reporting `selftest_error`); success is agreed with an
+    internally: it raises on every rank together), then the driver's `selftest()`, if it has one, runs -- LOCAL, so it may
+    fail on one rank alone; its exception is kept, not propagated, and the object held.  Success is agreed with an
     all-reduce, and after a failed agreement EVERY rank -- with or without a driver of its own -- runs the same collective
     tear-down before the next candidate's constructor starts its own collectives.  Returns (driver, name) or (None, None)."""
     import torch
@@ -145,7 +157,8 @@ def _agree_on_driver(candidates, make, rank: int, world: int, group, what: str):
         drv, err = None, None
         try:
             drv = make(cand)
-            err = getattr(drv, "selftest_error", None)
+            if hasattr(drv, "selftest"):
+                drv.selftest()
         except Exception as e:  # noqa: BLE001
             err = e
         flag = torch.tensor([0 if err else 1], device=dev)
@@ -158,39 +171,76 @@ def _agree_on_driver(candidates, make, rank: int, world: int, group, what: str):
     return None, None
 
 
-class RcclSlabDriver:
-    """The C sample loop of pmg_dist.c: RCCL send/recv called straight from the host library, comm stream + events,
-    no Python in the loop.  The 128-byte ncclUniqueId of rank 0 is broadcast through torch.distributed."""
+class SlabDriver:
+    """A transport object of pmg_dist.c and its C sample loop, no Python in the loop.  kind "ipc": boundary planes are
+    stored device-to-device straight into the neighbour's receive block (hipIpc memory) and announced by flag words;
+    kind "rccl": RCCL send/recv called straight from the host library, comm stream + events.  Both are built by
+    the library's collective bootstrap (pmg_rowblock.c) over a byte all-gather on torch.distributed: it agrees after every
+    step that can fail on one rank alone and raises PMGError ("... failed on rank r") on EVERY rank together, the half-built objects torn
+    down in step.  grid None: a transport without a slab.  loopback (world 1): the rank is its own z-neighbour for the
+    halo, nothing is collective."""
 
-    def __init__(self, grid, rank: int, world: int, loopback: bool = False, group=None):
+    def __init__(self, kind: str, grid, rank: int, world: int, group=None, loopback: bool = False):
         import ctypes as C
 
         from . import capi
         from .capi import check, lib
 
         self._h = C.c_void_p()
-        self._world, self._group = world, group
+        self.kind, self._grid, self._rank = kind, grid, rank  # the grid is kept alive
+        self._world, self._group = (1 if loopback else world), group
+        g = grid._h if grid is not None else None
         path = capi.torch_rccl_path()
-        pbytes = path.encode() if path else None
-        uid = None
-        if world > 1 or loopback:
-            buf = C.create_string_buffer(128)
-            err = None
-            if rank == 0:
-                try:
-                    check(lib.pmg_dist_get_unique_id(pbytes, buf))
-                except Exception as e:  # noqa: BLE001 -- the other ranks are about to enter the broadcast: tell them
-                    err = f"{type(e).__name__}: {e}"
-            payload = [None if err else bytes(buf.raw)]
-            if world > 1:
-                import torch.distributed as dist
+        path = path.encode() if path else None
+        if loopback and kind == "ipc":
+            check(lib.pmg_dist_create_ipc(g, 0, 1, C.byref(self._h)))
+            check(lib.pmg_dist_ipc_connect_loopback(self._h))
+        elif loopback:
+            uid = C.create_string_buffer(128)
+            check(lib.pmg_dist_get_unique_id(path, uid))
+            check(lib.pmg_dist_create(g, rank, world, uid, path, 1, C.byref(self._h)))
+        else:
+            self._comm = capi.torch_host_comm(rank, world, group)  # (pmg_host_comm, its callback): alive as long as the handle
+            check(lib.pmg_dist_create_comm(C.byref(self._comm[0]), kind.encode(), g, path, C.byref(self._h)))
 
-                dist.broadcast_object_list(payload, src=0, group=group)
-            if payload[0] is None:
-                raise RuntimeError(err or "rank 0 could not create the RCCL unique id")
-            uid = C.create_string_buffer(payload[0], 128)
-        check(lib.pmg_dist_create(grid._h if grid is not None else None, rank, world, uid, pbytes, int(loopback), C.byref(self._h)))  # grid None: a transport without a slab
-        self._grid = grid  # keep alive
+    def selftest(self):
+        """ipc only (ncclCommInitRank has connected RCCL's peers itself).  One round trip of a known pattern with both
+        z-neighbours (peer copies into their blocks, flag words, copy out) plus the all-gather pattern: if peer access or
+        the flags do not work on this machine this raises -- on every rank, the wait gives up after about a minute -- and
+        _agree_on_driver moves on to the next transport.  LOCAL: it can fail on one rank alone and no collective follows."""
+        if self.kind != "ipc":
+            return
+        import ctypes as C
+
+        import torch
+
+        from .capi import check, lib
+        from .wrappers import _ptr, _stream
+
+        rank, world = self._rank, self._world
+        n = 4096
+        send = torch.full((2, n), float(rank + 1), dtype=torch.float64, device="cuda") + torch.arange(n, dtype=torch.float64, device="cuda") / n
+        recv = torch.zeros((2, n), dtype=torch.float64, device="cuda")
+        P, I64 = C.c_void_p * 1, C.c_int64 * 1
+        nn = I64(n)
+        check(lib.pmg_dist_exchange(self._h, 1, P(_ptr(send[0])), nn, P(_ptr(recv[0])), nn, P(_ptr(send[1])), nn, P(_ptr(recv[1])), nn, _stream()))
+        torch.cuda.synchronize()
+        frac = torch.arange(n, dtype=torch.float64, device="cuda") / n
+        if rank > 0 and not torch.equal(recv[0], float(rank) + frac):
+            raise RuntimeError("ipc halo self-test: wrong data from the low neighbour")
+        if rank < world - 1 and not torch.equal(recv[1], float(rank + 2) + frac):
+            raise RuntimeError("ipc halo self-test: wrong data from the high neighbour")
+        # all-gather (all-peer mappings for more than two ranks): rank r contributes 64 + r values
+        counts = [64 + r for r in range(world)]
+        offs = [sum(counts[:r]) for r in range(world)]
+        buf = torch.zeros(sum(counts), dtype=torch.float64, device="cuda")
+        buf[offs[rank]:offs[rank] + counts[rank]] = float(rank + 1)
+        A64 = C.c_int64 * world
+        check(lib.pmg_dist_allgather(self._h, _ptr(buf), A64(*offs), A64(*counts), _stream()))
+        torch.cuda.synchronize()
+        want = torch.cat([torch.full((counts[r],), float(r + 1), dtype=torch.float64, device="cuda") for r in range(world)])
+        if not torch.equal(buf, want):
+            raise RuntimeError("ipc halo self-test: all-gather returned wrong data")
 
     def sample_cvec(self, b, y, its, scaled, sweep_type, seed, counter0):
         import ctypes as C
@@ -237,116 +287,22 @@ class RcclSlabDriver:
 
     def destroy(self):
         """Collective, orderly tear-down: unmap the peers' blocks, barrier, free the own block."""
-        if not self._h:
-            return
-        _teardown(self, getattr(self, "_world", 1), getattr(self, "_group", None))
+        if self._h:
+            _teardown(self, self._world, self._group)
 
     def __del__(self):
         try:
-            import ctypes as C
-
-            from .capi import lib
-
-            if self._h:
-                lib.pmg_dist_destroy(C.byref(self._h))
+            self.free()
         except Exception:
             pass
 
 
-class IpcSlabDriver(RcclSlabDriver):
-    """The C sample loop of pmg_dist.c with the "ipc" transport: boundary planes are stored device-to-device straight
-    into the neighbour's receive block (hipIpc memory) and announced by flag words; torch.distributed only carries
-    the bootstrap (all-gather of the handle blobs, one barrier)."""
+def RcclSlabDriver(grid, rank: int, world: int, loopback: bool = False, group=None):
+    return SlabDriver("rccl", grid, rank, world, group, loopback)
 
-    def __init__(self, grid, rank: int, world: int, group=None, loopback: bool = False):
-        import ctypes as C
-        import os
 
-        from .capi import check, lib
-
-        self._h = C.c_void_p()
-        self._grid = grid
-        self._world, self._group = (1 if loopback else world), group
-        if loopback:
-            check(lib.pmg_dist_create_ipc(grid._h if grid is not None else None, 0, 1, C.byref(self._h)))
-            check(lib.pmg_dist_ipc_connect_loopback(self._h))
-            return
-        import torch.distributed as dist
-
-        # every step that can fail on ONE rank alone (allocation, export, opening a peer's handle) is followed by an
-        # agreement, so that no rank is left waiting in a collective the failing rank never enters
-        err, blob, nb = None, None, C.c_int32()
-        try:  # local phase: allocate the receive block, export its handle
-            check(lib.pmg_dist_create_ipc(grid._h if grid is not None else None, rank, world, C.byref(self._h)))
-            check(lib.pmg_dist_ipc_blob_bytes(C.byref(nb)))
-            blob = C.create_string_buffer(nb.value)
-            check(lib.pmg_dist_ipc_export(self._h, blob))
-        except Exception as e:  # noqa: BLE001
-            err = f"{type(e).__name__}: {e}"
-        def agree(err, what):  # raises on every rank together: all of them tear the half-built transport down in step
-            try:
-                _all_ok(err, group, what)
-            except Exception:
-                _teardown(self, world, group)
-                raise
-
-        agree(err, "ipc: allocating / exporting the receive block")
-        blobs = [None] * world
-        dist.all_gather_object(blobs, bytes(blob.raw), group=group)
-        try:  # local phase: map the neighbours' (all peers') blocks
-            lo = C.create_string_buffer(blobs[rank - 1], nb.value) if rank > 0 else None
-            hi = C.create_string_buffer(blobs[rank + 1], nb.value) if rank < world - 1 else None
-            check(lib.pmg_dist_ipc_connect(self._h, lo, hi))
-            if world > 2:  # all-peer mappings: the all-gather of the distributed V-cycle becomes one step
-                bufs = [C.create_string_buffer(b_, nb.value) for b_ in blobs]
-                arr = (C.c_void_p * world)(*[C.cast(b_, C.c_void_p) for b_ in bufs])
-                check(lib.pmg_dist_ipc_connect_all(self._h, arr))
-        except Exception as e:  # noqa: BLE001
-            err = f"{type(e).__name__}: {e}"
-        agree(err, "ipc: opening the peers' memory handles")
-        dist.barrier(group=group)
-        # the self-test can fail on ONE rank alone and no collective follows inside this constructor: the failure is kept,
-        # not raised, so that the caller (_agree_on_driver) still holds the object for the collective tear-down
-        self.selftest_error = None
-        try:
-            self._selftest(rank, world)
-        except Exception as e:  # noqa: BLE001
-            self.selftest_error = e
-
-    def _selftest(self, rank, world):
-        """One round trip of a known pattern with both z-neighbours (peer copies into their blocks, flag words, copy
-        out): if peer access or the flags do not work on this machine the constructor fails -- on every rank, the
-        wait gives up after about a minute -- and DistGridSampler moves on to the next transport."""
-        import ctypes as C
-
-        import torch
-
-        from .capi import check, lib
-        from .wrappers import _ptr, _stream
-
-        n = 4096
-        send = torch.full((2, n), float(rank + 1), dtype=torch.float64, device="cuda") + torch.arange(n, dtype=torch.float64, device="cuda") / n
-        recv = torch.zeros((2, n), dtype=torch.float64, device="cuda")
-        P, I64 = C.c_void_p * 1, C.c_int64 * 1
-        nn = I64(n)
-        check(lib.pmg_dist_exchange(self._h, 1, P(_ptr(send[0])), nn, P(_ptr(recv[0])), nn, P(_ptr(send[1])), nn, P(_ptr(recv[1])), nn, _stream()))
-        torch.cuda.synchronize()
-        frac = torch.arange(n, dtype=torch.float64, device="cuda") / n
-        if rank > 0 and not torch.equal(recv[0], float(rank) + frac):
-            raise RuntimeError("ipc halo self-test: wrong data from the low neighbour")
-        if rank < world - 1 and not torch.equal(recv[1], float(rank + 2) + frac):
-            raise RuntimeError("ipc halo self-test: wrong data from the high neighbour")
-        # all-gather (all-peer mappings for more than two ranks): rank r contributes 64 + r values
-        counts = [64 + r for r in range(world)]
-        offs = [sum(counts[:r]) for r in range(world)]
-        buf = torch.zeros(sum(counts), dtype=torch.float64, device="cuda")
-        buf[offs[rank]:offs[rank] + counts[rank]] = float(rank + 1)
-        A64 = C.c_int64 * world
-        check(lib.pmg_dist_allgather(self._h, _ptr(buf), A64(*offs), A64(*counts), _stream()))
-        torch.cuda.synchronize()
-        want = torch.cat([torch.full((counts[r],), float(r + 1), dtype=torch.float64, device="cuda") for r in range(world)])
-        if not torch.equal(buf, want):
-            raise RuntimeError("ipc halo self-test: all-gather returned wrong data")
+def IpcSlabDriver(grid, rank: int, world: int, group=None, loopback: bool = False):
+    return SlabDriver("ipc", grid, rank, world, group, loopback)
 
 
 class DistGridSampler:
@@ -379,7 +335,7 @@ class DistGridSampler:
             # preference: ipc (peer copies, lowest latency) -> rccl (ncclSend/ncclRecv) -> torch P2P; every rank must
             # take the same path, so success is agreed with an all-reduce after each attempt
             candidates = [want] if want else (["ipc", "rccl"] if on_gpu else [])
-            drv, name = _agree_on_driver(candidates, lambda cand: IpcSlabDriver(self.grid, rank, world, group=group) if cand == "ipc" else RcclSlabDriver(self.grid, rank, world, group=group), rank, world, group, "halo exchange")
+            drv, name = _agree_on_driver(candidates, lambda cand: SlabDriver(cand, self.grid, rank, world, group), rank, world, group, "halo exchange")
             if drv is not None:
                 self.rccl, self.transport = drv, name
 
@@ -389,7 +345,7 @@ class DistGridSampler:
             self.rccl.check()
 
     def describe(self, lo_device: int = -1, hi_device: int = -1) -> dict:
-        """this rank's entry of a multi-GPU bench record (see RcclSlabDriver.describe); the torch P2P loop has no C object"""
+        """this rank's entry of a multi-GPU bench record (see SlabDriver.describe); the torch P2P loop has no C object"""
         if self.rccl is not None:
             return self.rccl.describe(lo_device, hi_device)
         import torch
@@ -495,7 +451,7 @@ def _rbh_mgmc(comm, transport, levels, replicate_below: int, coloring: int = 0):
     """The pmg_rbh_* call sequence of a hierarchy of MATMPIAIJ levels: levels[l] = dict(n=global rows, row0=, A=(rowptr,
     colidx_global, vals) of this rank's rows, P=(rowptr, colidx_global_coarse, vals) of this rank's rows of P_l (l >= 1)),
     level 0 = coarsest; the C side copies them.  Returns (rbh, mgmc): the pmg_mgmc handle borrows the hierarchy's arrays
-    until pmg_mgmc_setup, destroy rbh after it.  Collective over the ranks of `comm`."""
+    until its set-up, destroy rbh after it.  Collective over the ranks of `comm`."""
     import ctypes as C
 
     import numpy as np
@@ -519,6 +475,109 @@ def _rbh_mgmc(comm, transport, levels, replicate_below: int, coloring: int = 0):
         lib.pmg_rbh_destroy(C.byref(rbh))
         raise
     return rbh, mg
+
+
+class _RowBlockMGMC:
+    """The pmg_mgmc object of a row-block hierarchy (`levels` as for _rbh_mgmc) on the transport `drv`, a SlabDriver that
+    its owner keeps and destroys AFTER this object.  Collective over the driver's group, from creation to set-up."""
+
+    def __init__(self, drv, levels, replicate_below: int, coloring: int = 0):
+        import ctypes as C
+
+        import numpy as np
+
+        from .capi import RbhLevelView, check, lib
+
+        self._group, self._h = drv._group, None
+        self._rbh, self._h = _rbh_mgmc(drv._comm[0], drv._h, levels, replicate_below, coloring)
+        fold, views = C.c_int32(), [RbhLevelView() for _ in levels]
+        check(lib.pmg_rbh_get_info(self._rbh, None, C.byref(fold)))
+        for l, v_ in enumerate(views):
+            check(lib.pmg_rbh_get_level(self._rbh, l, C.byref(v_)))
+        self.fold, self.starts = fold.value, [np.ctypeslib.as_array(v_.starts, shape=(drv._world + 1,)).copy() for v_ in views]
+        top = views[-1]
+        self.n_owned, self.n_local = top.nowned, top.nlocal
+        self.row_range = (top.row0, top.row0 + top.nowned)
+        self.levels = len(levels)
+
+    def set_smoother(self, scaled: bool, omega: float = 1.0, sweep_type: int = SOR_FORWARD_SWEEP, its: int = 1):
+        from .capi import check, lib
+
+        check(lib.pmg_mgmc_set_smoother(self._h, int(scaled), omega, sweep_type, its))
+
+    def set_correction_form(self, literal: bool):
+        from .capi import check, lib
+
+        check(lib.pmg_mgmc_set_correction_form(self._h, int(literal)))
+
+    def algorithmic_bytes(self):
+        """(this rank's algorithmic bytes of one sample, per level): pmg_mgmc_get_algorithmic_bytes"""
+        import ctypes as C
+
+        import numpy as np
+
+        from .capi import check, lib
+
+        tot, per = C.c_double(), np.zeros(self.levels)
+        check(lib.pmg_mgmc_get_algorithmic_bytes(self._h, C.byref(tot), per.ctypes.data))
+        return tot.value, per
+
+    def set_lowrank(self, B_owned, S):
+        """MATLRC fine operator A + B diag(S) B^T, propagated to every level with the hierarchy's own restriction
+        (reference src/pc_gamgmc.c:157-196): B_owned = this rank's rows of B (n_owned x k).  Before setup()."""
+        import numpy as np
+
+        from .capi import check, lib
+
+        B = np.asarray(B_owned, np.float64)
+        S = np.ascontiguousarray(S, np.float64)
+        assert B.shape == (self.n_owned, len(S))
+        Bl = np.zeros((self.n_local, len(S)), order="F")
+        Bl[: self.n_owned] = B
+        check(lib.pmg_mgmc_set_lowrank(self._h, len(S), Bl.ctypes.data, S.ctypes.data))
+
+    def setup(self):
+        import ctypes as C
+
+        from .capi import check, lib
+
+        err = None
+        try:
+            check(lib.pmg_mgmc_setup(self._h))
+        except Exception as e:  # noqa: BLE001
+            err = e
+        _all_ok(err, self._group, "row-block hierarchy set-up")
+        lib.pmg_rbh_destroy(C.byref(self._rbh))  # the arrays were borrowed until set-up
+        return self
+
+    def sample(self, b_owned, y_owned, its: int, seed: int, counter0: int = 0, guesszero: bool = False) -> int:
+        """`its` samples; b_owned, y_owned: this rank's rows of the finest level (device tensors, y updated in place).  The
+        hierarchy's vectors have one entry per LOCAL row of the finest level (ghost entries ignored)."""
+        import ctypes as C
+
+        import torch
+
+        from .capi import check, lib
+        from .wrappers import _ptr, _stream
+
+        b = torch.zeros(self.n_local, dtype=torch.float64, device="cuda")
+        y = torch.zeros(self.n_local, dtype=torch.float64, device="cuda")
+        b[: self.n_owned] = b_owned
+        y[: self.n_owned] = y_owned
+        out = C.c_uint64()
+        check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), None, None, _stream()))
+        y_owned.copy_(y[: self.n_owned])
+        return out.value
+
+    def destroy(self):
+        import ctypes as C
+
+        from .capi import lib
+
+        if getattr(self, "_h", None):
+            lib.pmg_mgmc_destroy(C.byref(self._h))
+        if getattr(self, "_rbh", None):  # no set-up ran
+            lib.pmg_rbh_destroy(C.byref(self._rbh))
 
 
 class DistMCSOR:
@@ -579,7 +638,7 @@ class DistMCSOR:
         want_tr = transport or os.environ.get("PMG_DIST_TRANSPORT")
         if world > 1 and want_tr != "torch":
             on_gpu = dist.get_backend(group) == "nccl"
-            drv, name = _agree_on_driver([want_tr] if want_tr else (["ipc", "rccl"] if on_gpu else []), lambda cand: IpcSlabDriver(None, rank, world, group=group) if cand == "ipc" else RcclSlabDriver(None, rank, world, group=group), rank, world, group, "row-block sampler")
+            drv, name = _agree_on_driver([want_tr] if want_tr else (["ipc", "rccl"] if on_gpu else []), lambda cand: SlabDriver(cand, None, rank, world, group), rank, world, group, "row-block sampler")
             if drv is not None:
                 self._drv, self.transport = drv, name
         send_ptr, counts, recv_ptr, recv_src = plan["send_ptr"], plan["counts"], plan["recv_ptr"], plan["recv_src"]
@@ -704,7 +763,7 @@ class DistMCSOR:
             pass
 
 
-class DistAIJMGMC:
+class DistAIJMGMC(_RowBlockMGMC):
     """MGMC sampler on a caller-supplied hierarchy of assembled MATAIJ matrices distributed by ROW BLOCKS, one rank per
     device: the reference's PCGAMGMC on a MATMPIAIJ (src/pc_gamgmc.c:157-223; level sampler MCSORApply_MPIAIJ,
     src/mc_sor.c:298-381).  `operators[l]` = global CSR triple of level l (0 = coarsest), `interpolations[l]` (l >= 1) =
@@ -715,17 +774,13 @@ class DistAIJMGMC:
     which is factored redundantly: there every rank runs the single-device kernels on identical data, which costs less
     than a ghost update per colour for a few thousand rows.  The whole sample loop -- colour
     sweeps, ghost updates, residuals, transfers, coarse solve -- runs in C (pmg_mgmc.c) on the stream; this class only
-    slices the matrices, the set-up is pmg_rowblock.c's (pmg_rbh_*; host code, collective) -- the one the adapter reaches
-    through CRowBlock's route.  Bit-identical to MGMC.from_hierarchy."""
+    agrees on a transport and slices the matrices, the rest is _RowBlockMGMC: the set-up of pmg_rowblock.c (pmg_rbh_*;
+    host code, collective) that CRowBlock.mgmc and the adapter reach too.  Bit-identical to MGMC.from_hierarchy."""
 
     def __init__(self, operators, interpolations, rank: int, world: int, group=None, transport=None, starts=None, replicate_below: int = 50000, coloring: int = 0):
-        import ctypes as C
         import os
 
         import numpy as np
-
-        from . import capi
-        from .capi import RbhLevelView, check, lib
 
         self.rank, self.world, self.group = rank, world, group
         L = len(operators)
@@ -733,7 +788,7 @@ class DistAIJMGMC:
         n = [len(op[0]) - 1 for op in operators]
         # --- transport: the generic all-gather of pmg_dist.c ("ipc" peer stores or RCCL), agreed between the ranks
         want_tr = transport or os.environ.get("PMG_DIST_TRANSPORT")
-        self._drv, self.transport = _agree_on_driver([want_tr] if want_tr else ["ipc", "rccl"], lambda cand: IpcSlabDriver(None, rank, world, group=group) if cand == "ipc" else RcclSlabDriver(None, rank, world, group=group), rank, world, group, "row-block hierarchy")
+        self._drv, self.transport = _agree_on_driver([want_tr] if want_tr else ["ipc", "rccl"], lambda cand: SlabDriver(cand, None, rank, world, group), rank, world, group, "row-block hierarchy")
         if self._drv is None:
             raise RuntimeError("DistAIJMGMC needs the 'ipc' or 'rccl' transport of the HIP library")
         # --- this rank's rows of every level, global columns, entries in the caller's order (the summation order of a row);
@@ -747,97 +802,10 @@ class DistAIJMGMC:
             return rp[r0:r1 + 1] - rp[r0], ci[rp[r0]:rp[r1]], v[rp[r0]:rp[r1]]
 
         cut = [(int(starts[l][rank]), int(starts[l][rank + 1])) for l in range(L)]
-        self._comm = capi.torch_host_comm(rank, world, group)  # (pmg_host_comm, its callback): alive while the C side may call back
-        self._h = None
-        self._rbh, self._h = _rbh_mgmc(self._comm[0], self._drv._h, [dict(n=n[l], row0=cut[l][0], A=rows(operators[l], *cut[l]), P=rows(interpolations[l], *cut[l]) if l >= 1 else None) for l in range(L)], replicate_below, coloring)
-        fold, views = C.c_int32(), [RbhLevelView() for _ in range(L)]
-        check(lib.pmg_rbh_get_info(self._rbh, None, C.byref(fold)))
-        for l in range(L):
-            check(lib.pmg_rbh_get_level(self._rbh, l, C.byref(views[l])))
-        self.fold, self.starts = fold.value, [np.ctypeslib.as_array(v_.starts, shape=(world + 1,)).copy() for v_ in views]
-        top = views[L - 1]
-        self.n_owned, self.n_local = top.nowned, top.nlocal
-        self.row_range = (top.row0, top.row0 + top.nowned)
-        self.levels = L
-
-    def set_smoother(self, scaled: bool, omega: float = 1.0, sweep_type: int = SOR_FORWARD_SWEEP, its: int = 1):
-        from .capi import check, lib
-
-        check(lib.pmg_mgmc_set_smoother(self._h, int(scaled), omega, sweep_type, its))
-
-    def set_correction_form(self, literal: bool):
-        from .capi import check, lib
-
-        check(lib.pmg_mgmc_set_correction_form(self._h, int(literal)))
-
-    def algorithmic_bytes(self):
-        """(this rank's algorithmic bytes of one sample, per level): pmg_mgmc_get_algorithmic_bytes"""
-        import ctypes as C
-
-        import numpy as np
-
-        from .capi import check, lib
-
-        tot, per = C.c_double(), np.zeros(self.levels)
-        check(lib.pmg_mgmc_get_algorithmic_bytes(self._h, C.byref(tot), per.ctypes.data))
-        return tot.value, per
-
-    def set_lowrank(self, B_owned, S):
-        """MATLRC fine operator A + B diag(S) B^T, propagated to every level with the hierarchy's own restriction
-        (reference src/pc_gamgmc.c:157-196): B_owned = this rank's rows of B (n_owned x k).  Before setup()."""
-        import numpy as np
-
-        from .capi import check, lib
-
-        B = np.asarray(B_owned, np.float64)
-        S = np.ascontiguousarray(S, np.float64)
-        assert B.shape == (self.n_owned, len(S))
-        Bl = np.zeros((self.n_local, len(S)), order="F")
-        Bl[: self.n_owned] = B
-        check(lib.pmg_mgmc_set_lowrank(self._h, len(S), Bl.ctypes.data, S.ctypes.data))
-
-    def setup(self):
-        import ctypes as C
-
-        from .capi import check, lib
-
-        err = None
-        try:
-            check(lib.pmg_mgmc_setup(self._h))
-        except Exception as e:  # noqa: BLE001
-            err = e
-        _all_ok(err, self.group, "row-block hierarchy set-up")
-        lib.pmg_rbh_destroy(C.byref(self._rbh))  # the arrays were borrowed until set-up
-        return self
-
-    def sample(self, b_owned, y_owned, its: int, seed: int, counter0: int = 0, guesszero: bool = False) -> int:
-        """`its` samples; b_owned, y_owned: this rank's rows of the finest level (device tensors, y updated in place)"""
-        import ctypes as C
-
-        import torch
-
-        from .capi import check, lib
-        from .wrappers import _ptr, _stream
-
-        b = torch.zeros(self.n_local, dtype=torch.float64, device="cuda")
-        y = torch.zeros(self.n_local, dtype=torch.float64, device="cuda")
-        b[: self.n_owned] = b_owned
-        y[: self.n_owned] = y_owned
-        out = C.c_uint64()
-        check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), None, None, _stream()))
-        y_owned.copy_(y[: self.n_owned])
-        return out.value
+        super().__init__(self._drv, [dict(n=n[l], row0=cut[l][0], A=rows(operators[l], *cut[l]), P=rows(interpolations[l], *cut[l]) if l >= 1 else None) for l in range(L)], replicate_below, coloring)
 
     def destroy(self):
-        import ctypes as C
-
-        from .capi import lib
-
-        if getattr(self, "_h", None) is not None and self._h:
-            lib.pmg_mgmc_destroy(C.byref(self._h))
-            self._h = None
-        if getattr(self, "_rbh", None):  # no set-up ran
-            lib.pmg_rbh_destroy(C.byref(self._rbh))
+        super().destroy()
         if getattr(self, "_drv", None) is not None:
             self._drv.destroy()  # collective: disconnect, barrier, destroy
             self._drv = None
@@ -847,9 +815,10 @@ class CRowBlock:
     """The multi-rank samplers on MATMPIAIJ row blocks reached through the C-ABI ALONE (pmg_rowblock.c): transport bootstrap,
     colouring, ghost plans, local operators and the sample loops are C; Python only supplies the byte all-gather callback
     (torch.distributed here, MPI_Allgather in adapter/, pipes in examples/pmg_bench.c) and device tensors.  This is what a
-    PETSc caller with an MPI_Comm uses.  DistMCSOR / DistAIJMGMC above take the same ghost plans and the same hierarchy from
-    pmg_rowblock.c (DistAIJMGMC through the call sequence of `mgmc` below); they differ in who slices the rows (they do, from
-    global matrices every rank holds) and who makes the transport (IpcSlabDriver / RcclSlabDriver over torch.distributed).
+    PETSc caller with an MPI_Comm uses.  DistMCSOR / DistAIJMGMC above take the same transport
+    (SlabDriver), the same ghost plans and the same hierarchy (_RowBlockMGMC) from pmg_rowblock.c; they differ in
+    who slices the rows (they do, from global matrices every rank holds) and in that they fall back from one transport to
+    the next after a self-test (_agree_on_driver), where `transport` here is taken as given.
 
       CRowBlock.sampler(...)  MCSORCreate + MCSORSetUp + the sample loop on a MATMPIAIJ (reference src/mc_sor.c:298-381,553-605)
       CRowBlock.mgmc(...)     PCGAMGMC on a hierarchy of MATMPIAIJ levels (src/pc_gamgmc.c:157-264)"""
@@ -857,21 +826,15 @@ class CRowBlock:
     def __init__(self, rank: int, world: int, group=None, transport: str = "ipc"):
         import ctypes as C
 
-        from . import capi
-        from .capi import check, lib
-
-        self.rank, self.world = rank, world
-        self.comm, self._keep = capi.torch_host_comm(rank, world, group)
-        self._dist = C.c_void_p()
-        path = capi.torch_rccl_path()
-        check(lib.pmg_dist_create_comm(C.byref(self.comm), transport.encode(), None, path.encode() if path else None, C.byref(self._dist)))
-        self.transport = transport
-        self._mc, self._dm, self._mg, self._rbh = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self.rank, self.world, self.transport = rank, world, transport
+        self._drv = SlabDriver(transport, None, rank, world, group)
+        self.comm = self._drv._comm[0]
+        self._mc, self._dm, self._mg = C.c_void_p(), C.c_void_p(), None
         self.nowned = 0
 
     @property
     def dist_handle(self):
-        return self._dist
+        return self._drv._h
 
     def sampler(self, row_starts, rowptr, colidx_global, vals, omega=1.0, colors=None, ncolors=0):
         """this rank's rows with GLOBAL columns (pmg_rowblock_merge_mpiaij of MatMPIAIJGetSeqAIJ's blocks); colors None: the
@@ -886,7 +849,7 @@ class CRowBlock:
         rp, ci, v = np.ascontiguousarray(rowptr, np.int64), np.ascontiguousarray(colidx_global, np.int64), np.ascontiguousarray(vals, np.float64)
         col = None if colors is None else np.ascontiguousarray(colors, np.int32)
         self.nowned = int(rs[self.rank + 1] - rs[self.rank])
-        check(lib.pmg_rowblock_sampler_create(C.byref(self.comm), self._dist, rs.ctypes.data, rp.ctypes.data, ci.ctypes.data, v.ctypes.data, 64, ncolors, col.ctypes.data if col is not None else None, omega, C.byref(self._mc), C.byref(self._dm)))
+        check(lib.pmg_rowblock_sampler_create(C.byref(self.comm), self.dist_handle, rs.ctypes.data, rp.ctypes.data, ci.ctypes.data, v.ctypes.data, 64, ncolors, col.ctypes.data if col is not None else None, omega, C.byref(self._mc), C.byref(self._dm)))
         return self
 
     def sample(self, b_owned, y_owned, its: int, seed: int, counter0: int = 0, scaled: bool = True, sweep_type: int = SOR_FORWARD_SWEEP) -> int:
@@ -895,13 +858,10 @@ class CRowBlock:
         from .capi import check, lib
         from .wrappers import _ptr, _stream
 
+        if self._mg is not None:
+            return self._mg.sample(b_owned, y_owned, its, seed, counter0)
         out = C.c_uint64()
-        if self._mg:  # the hierarchy's vectors have one entry per LOCAL row of the finest level (ghost entries ignored)
-            bp, yp = self._pad(b_owned), self._pad(y_owned)  # both stay referenced until the call has been enqueued
-            check(lib.pmg_mgmc_sample(self._mg, _ptr(bp), _ptr(yp), its, 0, seed, counter0, C.byref(out), None, None, _stream()))
-            y_owned.copy_(yp[: self.nowned])
-        else:
-            check(lib.pmg_distmcsor_sample(self._dm, self.nowned, _ptr(b_owned), _ptr(y_owned), its, int(scaled), sweep_type, seed, counter0, C.byref(out), _stream()))
+        check(lib.pmg_distmcsor_sample(self._dm, self.nowned, _ptr(b_owned), _ptr(y_owned), its, int(scaled), sweep_type, seed, counter0, C.byref(out), _stream()))
         return out.value
 
     def apply(self, b_owned, y_owned, sweep_type: int = SOR_FORWARD_SWEEP):
@@ -910,41 +870,15 @@ class CRowBlock:
 
         check(lib.pmg_distmcsor_apply(self._dm, self.nowned, _ptr(b_owned), _ptr(y_owned), sweep_type, _stream()))
 
-    def _pad(self, t):
-        import torch
-
-        p = torch.zeros(self.nlocal, dtype=torch.float64, device="cuda")
-        p[: self.nowned] = t
-        return p
-
     def mgmc(self, levels, replicate_below: int = 50000, smoother=(True, 1.0, SOR_FORWARD_SWEEP, 1), lowrank=None):
         """levels[l] = dict(n=global rows, row0=, A=(rowptr, colidx_global, vals) of this rank's rows, P=(rowptr,
         colidx_global_coarse, vals) of this rank's rows of P_l (l >= 1)); level 0 = coarsest"""
-        import ctypes as C
-
-        import numpy as np
-
-        from .capi import RbhLevelView, check, lib
-
-        L = len(levels)
-        self._rbh, self._mg = _rbh_mgmc(self.comm, self._dist, levels, replicate_below)
-        check(lib.pmg_mgmc_set_smoother(self._mg, int(smoother[0]), smoother[1], smoother[2], smoother[3]))
-        view = RbhLevelView()
-        check(lib.pmg_rbh_get_level(self._rbh, L - 1, C.byref(view)))
-        self.nowned, self.nlocal = view.nowned, view.nlocal
+        self._mg = _RowBlockMGMC(self._drv, levels, replicate_below)
+        self.nowned, self.nlocal = self._mg.n_owned, self._mg.n_local
+        self._mg.set_smoother(*smoother)
         if lowrank is not None:
-            B, S = lowrank
-            Bl = np.zeros((self.nlocal, len(S)), order="F")
-            Bl[: self.nowned] = B
-            S = np.ascontiguousarray(S, np.float64)
-            check(lib.pmg_mgmc_set_lowrank(self._mg, len(S), Bl.ctypes.data, S.ctypes.data))
-        err = None
-        try:
-            check(lib.pmg_mgmc_setup(self._mg))
-        except Exception as e:  # noqa: BLE001
-            err = e
-        _all_ok(err, None, "row-block hierarchy set-up")
-        lib.pmg_rbh_destroy(C.byref(self._rbh))  # the arrays were borrowed until set-up
+            self._mg.set_lowrank(*lowrank)
+        self._mg.setup()
         return self
 
     def destroy(self):
@@ -953,13 +887,11 @@ class CRowBlock:
 
         from .capi import lib
 
-        if self._mg:
-            lib.pmg_mgmc_destroy(C.byref(self._mg))
+        if self._mg is not None:
+            self._mg.destroy()
         if self._dm:
             lib.pmg_distmcsor_destroy(C.byref(self._dm))
         if self._mc:
             lib.pmg_mcsor_destroy(C.byref(self._mc))
-        if self._rbh:
-            lib.pmg_rbh_destroy(C.byref(self._rbh))
-        if self._dist:
-            lib.pmg_dist_destroy_comm(C.byref(self.comm), C.byref(self._dist))
+        self._drv.destroy()
+

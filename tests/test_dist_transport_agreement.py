@@ -1,9 +1,9 @@
-"""world_size-2/3 `gloo` test (CPU) of the transport agreement of parmgmc_amd.dist: a transport whose constructor fails on
-ONE rank alone (the ipc self-test can: IpcSlabDriver._selftest) must be torn down with the SAME collectives on every
+"""world_size-2/3 `gloo` test (CPU) of the transport agreement of parmgmc_amd.dist: a transport that fails on
+ONE rank alone (the ipc self-test can: SlabDriver.selftest) must be torn down with the SAME collectives on every
 rank -- the rank without a driver included -- before the next candidate's constructor starts its own collectives.
 Round 2's DistAIJMGMC called the collective destroy() only where a driver existed: the failing rank went on into the next
 candidate's broadcast while its peers sat in a barrier (dist.py:770).  Drivers are fakes that record their
-calls and use the collectives the real constructors use (broadcast_object_list / barrier); nothing here touches a GPU."""
+calls and use the collectives the real constructor uses (all-gathers on the group); nothing here touches a GPU."""
 import os
 import socket
 
@@ -19,6 +19,7 @@ def _free_port():
 
 
 def _worker(rank, world, port, mode, q):
+    import torch
     import torch.distributed as dist
 
     from parmgmc_amd import dist as D
@@ -28,24 +29,27 @@ def _worker(rank, world, port, mode, q):
     dist.init_process_group("gloo", rank=rank, world_size=world)
     log = []
 
+    def allgather(value):
+        """the byte all-gather of capi.torch_host_comm: every collective of pmg_dist_create_comm is one of these"""
+        out = [torch.zeros(1, dtype=torch.int64) for _ in range(world)]
+        dist.all_gather(out, torch.tensor([value], dtype=torch.int64))
+        return [int(t) for t in out]
+
     class Fake:
-        """what the real drivers do at construction: ipc = all-gather + barrier, then a LOCAL self-test; rccl = a broadcast"""
+        """what the real driver does at construction (pmg_dist_create_comm): agreement, all-gather of the blobs / of rank 0's
+        unique id, agreement -- all-gathers on the group; then, for ipc, a LOCAL self-test as a method"""
 
         def __init__(self, name):
             self.name, self._h = name, 1
-            if name == "ipc":
-                blobs = [None] * world
-                dist.all_gather_object(blobs, f"blob{rank}")
-                dist.barrier()
-                self.selftest_error = None
-                if mode == "selftest_reports" and rank == 1:
-                    self.selftest_error = RuntimeError("ipc halo self-test: wrong data from the low neighbour")
-                if mode == "ctor_raises" and rank == 1:
-                    raise RuntimeError("peer access denied")
-            else:
-                payload = [f"uid-from-{rank}" if rank == 0 else None]
-                dist.broadcast_object_list(payload, src=0)
-                assert payload[0] == "uid-from-0"  # a rank that skipped a barrier would receive something else or hang
+            assert allgather(0) == [0] * world
+            assert allgather(100 * (name == "ipc") + rank) == [100 * (name == "ipc") + r for r in range(world)]  # a rank that skipped a barrier would receive something else or hang
+            assert allgather(0) == [0] * world
+            if name == "ipc" and mode == "ctor_raises" and rank == 1:
+                raise RuntimeError("peer access denied")
+
+        def selftest(self):
+            if self.name == "ipc" and mode == "selftest_reports" and rank == 1:
+                raise RuntimeError("ipc halo self-test: wrong data from the low neighbour")
 
         def disconnect(self):
             log.append((self.name, "disconnect"))

@@ -607,6 +607,87 @@ def test_a_chain_of_ipc_objects_in_one_process_reuses_its_receive_block():
         assert np.array_equal(got, yd.cpu().numpy()), f"object {it} of the chain"
 
 
+def _failed_selftest_worker(rank, world, port, q):
+    """step 1: the real ipc driver, its self-test failing on rank 1 alone, is dropped by the agreement; step 2: the next
+    sampler of the same process, which inherits the pooled receive block"""
+    import torch
+    import torch.distributed as dist
+
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    torch.cuda.set_device(0)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from parmgmc_amd import GridMCSOR
+    from parmgmc_amd.dist import DistGridSampler, IpcSlabDriver, _agree_on_driver
+    from parmgmc_amd.slab import slab_cuts
+
+    nx, ny, nz, kappa = 24, 10, 9, 1.5
+    cuts = slab_cuts(nz, world)
+    slab = GridMCSOR(nx, ny, nz, kappa, kz0=cuts[rank], nz_owned=cuts[rank + 1] - cuts[rank])
+    built = []
+
+    def failing_selftest():
+        if rank == 1:
+            raise ValueError("a self-test that fails on one rank alone")
+
+    def make(cand):
+        drv = IpcSlabDriver(slab, rank, world)
+        built.append(drv)
+        drv.selftest = failing_selftest
+        return drv
+
+    agreed = _agree_on_driver(["ipc"], make, rank, world, None, "test")
+    handles_null = [not d._h for d in built]
+
+    smp = DistGridSampler(nx, ny, nz, kappa, rank, world, transport="ipc")
+    assert smp.transport == "ipc"
+    g = smp.grid
+    rng = np.random.default_rng(5)
+    b_all, y_all = rng.standard_normal(nx * ny * nz), rng.standard_normal(nx * ny * nz)
+    lo, hi = g.kz0 * nx * ny, (g.kz0 + g.nz) * nx * ny
+    b = g.to_cvec(torch.as_tensor(b_all[lo:hi], device="cuda"))
+    y = g.to_cvec(torch.as_tensor(y_all[lo:hi], device="cuda"))
+    smp.sample_cvec(b, y, 5, seed=42, counter0=1)
+    torch.cuda.synchronize()
+    smp.check()
+    q.put((rank, agreed, handles_null, g.from_cvec(y).cpu().numpy()))
+    smp.destroy()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def test_an_ipc_driver_whose_selftest_fails_on_one_rank_is_torn_down_in_step():
+    """What the fakes of tests/test_dist_transport_agreement.py cannot show: the REAL ipc object (pmg_dist_create_comm, three
+    ranks, 24 x 10 x 9 slabs) is torn down collectively after its self-test raised on rank 1 alone -- every rank is left
+    without a transport and with a null handle --, and the pooled receive block it gives back is clean: the sampler built
+    next in the same process is the single-device chain bit for bit."""
+    import torch
+    import torch.multiprocessing as mp
+
+    from parmgmc_amd import GridMCSOR
+
+    nx, ny, nz, world = 24, 10, 9, 3
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = _free_port()
+    procs = [ctx.Process(target=_failed_selftest_worker, args=(r, world, port, q)) for r in range(world)]
+    for p in procs:
+        p.start()
+    parts = sorted((q.get(timeout=200) for _ in range(world)), key=lambda t: t[0])
+    for p in procs:
+        p.join(timeout=120)
+        assert p.exitcode == 0
+    for _, agreed, handles_null, _ in parts:
+        assert agreed == (None, None)
+        assert handles_null == [True]  # one driver was built on every rank, and the collective tear-down freed it
+    rng = np.random.default_rng(5)
+    b_all, y_all = rng.standard_normal(nx * ny * nz), rng.standard_normal(nx * ny * nz)
+    one = GridMCSOR(nx, ny, nz, 1.5)
+    yd = torch.as_tensor(y_all, device="cuda")
+    one.sample(torch.as_tensor(b_all, device="cuda"), yd, 5, seed=42, counter0=1)
+    assert np.array_equal(np.concatenate([x[3] for x in parts]), yd.cpu().numpy())
+
+
 def _bytes_worker(rank, world, port, grid, levels, q):
     import torch
     import torch.distributed as dist
