@@ -183,6 +183,58 @@ pmg_status pmg_mcsor_lowrank_sizes(pmg_mcsor mc, int32_t *k, int64_t *rows, int 
 pmg_status pmg_mcsor_destroy(pmg_mcsor *mc);
 
 /* ------------------------------------------------------------------------------------------------------ */
+/* Coloured block Gibbs: the multiplicative patch smoother of examples/ex13.py:11-22 (PCASM / ASMStarPC,   */
+/* local_type multiplicative, every patch a one-iteration Richardson around -sub_pc_type cholsampler,      */
+/* src/pc_chols.c:174-194 factor, :220-260 sample, :284-287 Richardson).  One patch update is              */
+/*   y_P <- A_PP^-1 (b_P - A_{P,rest} y_rest) + L_P^-T xi_P,   A_PP = L_P L_P^T,                            */
+/* an exact conditional draw, so blocks may overlap and rows may belong to no block (never written).       */
+/* ------------------------------------------------------------------------------------------------------ */
+typedef struct pmg_blockgibbs_s *pmg_blockgibbs;
+
+/* The operator is host CSR (borrowed until pmg_blockgibbs_setup returns); block p lists the rows blockrows[blockptr[p] ..
+   blockptr[p+1]) in the caller's order (copied).  A slot is one entry of blockrows: s = blockptr[p] + i, nslots =
+   blockptr[nblocks].  A_PP[i][j] is the stored entry (p_i, p_j) for i >= j, 0 where none is stored (the lower triangle, as
+   dpotrf('L') at src/pc_chols.c:188 reads it).  PMG_ERR_SUP: a block of more than 64 rows (the dense path's range,
+   src/pc_chols.c:33-35); PMG_ERR_ARG_OUTOFRANGE: an empty block, a row outside [0, n), a row twice in one block.
+   Sweep type = forward. */
+pmg_status pmg_blockgibbs_create_csr(int32_t n, const int32_t *rowptr_host, const int32_t *colidx_host, const double *vals_host, int32_t nblocks, const int32_t *blockptr_host, const int32_t *blockrows_host, pmg_blockgibbs *bg);
+/* Optional, before set-up: colour block_colors_host[p] in [0, ncolors) for every block (copied); NULL = the default, first-fit
+   over the blocks in block order.  Two blocks conflict if they share a row or if a row of one has a stored entry in a column
+   of the other, in either direction; pmg_blockgibbs_setup checks whatever colouring is used and fails with
+   PMG_ERR_ARG_WRONG, naming two conflicting blocks of one colour (the blocks of a colour are swept in one launch). */
+pmg_status pmg_blockgibbs_set_coloring(pmg_blockgibbs bg, int32_t ncolors, const int32_t *block_colors_host);
+/* Optional, before set-up: the vectors of apply / sample / sweep_xi are indexed by position pos_of_row_host[row] in [0, ld)
+   instead of by row (ld >= n, positions distinct; copied).  What a level of a hierarchy uses (pmg_mcsor_get_layout). */
+pmg_status pmg_blockgibbs_set_layout(pmg_blockgibbs bg, int32_t ld, const int32_t *pos_of_row_host);
+/* as pmg_mcsor_set_sweep_type (src/mc_sor.c:427): forward visits the block colours in ascending, backward in descending order,
+   symmetric = forward then backward, a draw each */
+pmg_status pmg_blockgibbs_set_sweep_type(pmg_blockgibbs bg, int type);
+pmg_status pmg_blockgibbs_get_sweep_type(pmg_blockgibbs bg, int *type);
+/* Colouring, Cholesky factor L_p and W_p = L_p^-1 of every block on the host (src/pc_chols.c:174-194), upload.
+   PMG_ERR_MAT_CH_ZRPVT, naming the block and the leading minor, when a pivot is not positive (src/pc_chols.c:190).
+   The getters below and the sweeps fail with PMG_ERR_ARG_WRONGSTATE before it, the setters after it. */
+pmg_status pmg_blockgibbs_setup(pmg_blockgibbs bg);
+pmg_status pmg_blockgibbs_get_num_colors(pmg_blockgibbs bg, int32_t *ncolors);
+pmg_status pmg_blockgibbs_get_coloring(pmg_blockgibbs bg, int32_t *block_colors_host); /* [nblocks] */
+pmg_status pmg_blockgibbs_get_num_slots(pmg_blockgibbs bg, int32_t *nslots);
+/* W_p = L_p^-1 of block p, row-major m x m (W_host: room for m * m <= 4096 doubles; NULL returns m only) */
+pmg_status pmg_blockgibbs_get_block_factor(pmg_blockgibbs bg, int32_t p, int32_t *m, double *W_host);
+/* One sweep of the handle's type with xi = 0: multiplicative Schwarz / block Gauss-Seidel (the deterministic part of
+   src/pc_chols.c:220-260 per patch).  r_i = b[p_i] - sum a_k y[col_k] over the stored entries of row p_i outside the block, in
+   storage order starting from b; y_P <- (W^T W) r, every row summed over j ascending from zero (bit-reproducible). */
+pmg_status pmg_blockgibbs_apply(pmg_blockgibbs bg, const double *b_dev, double *y_dev, void *stream);
+/* `its` samples (src/pc_chols.c:284-287 per patch): y_P <- (W^T W) r + W^T xi_P.  Slot s of the directional sweep with draw
+   counter c takes element s of the row stream (Philox counter (s >> 1, 0, c_lo, c_hi), key seed, element s & 1): the noise does
+   not depend on the colouring or the packing.  Counters as pmg_mcsor_sample: one per directional sweep from counter0. */
+pmg_status pmg_blockgibbs_sample(pmg_blockgibbs bg, const double *b_dev, double *y_dev, int32_t its, uint64_t seed, uint64_t counter0, uint64_t *counter_out, void *stream);
+/* diagnostic: ONE directional sweep (backward != 0: colours descending) with the normals read from xi_slots_dev[nslots] */
+pmg_status pmg_blockgibbs_sweep_xi(pmg_blockgibbs bg, int backward, const double *xi_slots_dev, const double *b_dev, double *y_dev, void *stream);
+/* bytes one noisy directional sweep needs: the factors as stored (rows of W^T W and of W^T, padded to the tile), 12 per
+   exterior entry, per slot 4 (position) + 8 (b) + 8 (y read) + 8 (y written) */
+pmg_status pmg_blockgibbs_get_algorithmic_bytes(pmg_blockgibbs bg, double *bytes);
+pmg_status pmg_blockgibbs_destroy(pmg_blockgibbs *bg);
+
+/* ------------------------------------------------------------------------------------------------------ */
 /* Matrix-free MCSOR on a DMDA grid: the same interface for the operator of                                */
 /* MatAssembleShiftedLaplaceFD (src/problems.c:14-75; 3-D analogue, nz = 1 is the reference 2-D matrix)    */
 /* ------------------------------------------------------------------------------------------------------ */
@@ -407,6 +459,17 @@ pmg_status pmg_mgmc_set_level_interpolation(pmg_mgmc mg, int32_t level, int32_t 
 pmg_status pmg_mgmc_set_rowblock_transport(pmg_mgmc mg, pmg_dist dist, const int64_t *coarse_starts);
 pmg_status pmg_mgmc_set_level_rowblock(pmg_mgmc mg, int32_t level, int64_t row0, int32_t nowned, int32_t ncolors, const int32_t *colors_owned, const int64_t *send_ptr, const int32_t *send_rows, const int64_t *counts, const int64_t *recv_ptr, const int32_t *recv_src, const int32_t *recv_rows);
 pmg_status pmg_mgmc_set_level_restriction(pmg_mgmc mg, int32_t level, int32_t nrows, int32_t ncols, const int32_t *rowptr, const int32_t *colidx, const double *vals);
+/* Block Gibbs smoothing of `level` of a handle from pmg_mgmc_create_hierarchy, before set-up: the multiplicative patch smoother
+   of examples/ex13.py:11-22 (PCASM multiplicative around -sub_pc_type cholsampler, src/pc_chols.c:174-194,220-260,284-287) as
+   the level smoother.  Blocks and colours as for pmg_blockgibbs_create_csr / _set_coloring (copied; block_colors NULL: first-fit;
+   checked at set-up against the level's operator, with pmg_blockgibbs' errors).  Any smoothed level: >= 1, and 0 when the coarse
+   sampler is Gibbs (else PMG_ERR_ARG_WRONG at set-up).  At set-up the level builds a pmg_blockgibbs on its operator in the layout
+   of its pmg_mcsor; residual and transfers stay, the smoothing legs run block sweeps: one draw counter per directional sweep
+   from the level's counter, key level_seed(seed, l), the slot stream of that level.  pmg_mgmc_level_sweep on such a level runs
+   the block sweep, pmg_mgmc_get_algorithmic_bytes charges pmg_blockgibbs_get_algorithmic_bytes per sweep.  A hierarchy without
+   block levels is untouched.  PMG_ERR_SUP, here or from the other call, whichever comes second: omega != 1
+   (pmg_mgmc_set_smoother), pmg_mgmc_set_lowrank, row-block levels or transport, DMDA handles; and pmg_mgmc_sample_chains*. */
+pmg_status pmg_mgmc_set_level_blocks(pmg_mgmc mg, int32_t level, int32_t nblocks, const int32_t *blockptr_host, const int32_t *blockrows_host, int32_t ncolors, const int32_t *block_colors_host_or_null);
 /* both for either PetscInt width (idx_width = 32 | 64) */
 pmg_status pmg_mgmc_set_level_operator_idx(pmg_mgmc mg, int32_t level, int64_t n, const void *rowptr_host, const void *colidx_host, const double *vals_host, int idx_width);
 pmg_status pmg_mgmc_set_level_interpolation_idx(pmg_mgmc mg, int32_t level, int64_t nrows, int64_t ncols, const void *rowptr_host, const void *colidx_host, const double *vals_host, int idx_width);

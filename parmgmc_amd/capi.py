@@ -308,6 +308,22 @@ _sig = {
     "pmg_chaincov_get_errors": (_int, [_vp, _i32, _i32, _vp]),
     "pmg_chaincov_get_reference": (_int, [_vp, _vp]),
     "pmg_chaincov_covariance": (_int, [_vp, _vp, _vp, _vp]),
+    "pmg_blockgibbs_create_csr": (_int, [_i32, _vp, _vp, _vp, _i32, _vp, _vp, C.POINTER(_vp)]),
+    "pmg_blockgibbs_set_coloring": (_int, [_vp, _i32, _vp]),
+    "pmg_blockgibbs_set_layout": (_int, [_vp, _i32, _vp]),
+    "pmg_blockgibbs_set_sweep_type": (_int, [_vp, _int]),
+    "pmg_blockgibbs_get_sweep_type": (_int, [_vp, C.POINTER(_int)]),
+    "pmg_blockgibbs_setup": (_int, [_vp]),
+    "pmg_blockgibbs_get_num_colors": (_int, [_vp, C.POINTER(_i32)]),
+    "pmg_blockgibbs_get_coloring": (_int, [_vp, _vp]),
+    "pmg_blockgibbs_get_num_slots": (_int, [_vp, C.POINTER(_i32)]),
+    "pmg_blockgibbs_get_block_factor": (_int, [_vp, _i32, C.POINTER(_i32), _vp]),
+    "pmg_blockgibbs_apply": (_int, [_vp, _vp, _vp, _vp]),
+    "pmg_blockgibbs_sample": (_int, [_vp, _vp, _vp, _i32, _u64, _u64, C.POINTER(_u64), _vp]),
+    "pmg_blockgibbs_sweep_xi": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
+    "pmg_blockgibbs_get_algorithmic_bytes": (_int, [_vp, C.POINTER(_dbl)]),
+    "pmg_blockgibbs_destroy": (_int, [C.POINTER(_vp)]),
+    "pmg_mgmc_set_level_blocks": (_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp]),
 }
 for _name, (_res, _args) in _sig.items():
     _f = getattr(lib, _name)

@@ -178,4 +178,36 @@ pmg_status pmg_chainstats_trace_window(pmg_chainstats cs, int32_t q, int32_t fir
 /* pmg_rowblock.c */
 void pmg_mcsor_adopt_arrays(pmg_mcsor mc, int32_t *rowptr, int32_t *colidx, double *vals);
 
+/* pmg_blockgibbs_host.c: everything pmg_blockgibbs_setup does on the host -- block extraction, the conflict graph and its
+   colouring, W_p = L_p^-1 of every block, the interior / exterior split of every block row, the packing into wavefront tiles
+   (kernels_blockgibbs.hip).  Host arrays only, freed by pmg_bg_plan_free.
+   A tile is one wavefront: 64 / g blocks of padded width g, lane (q, i) = q * g + i owns local row i of its q-th block. */
+#define PMG_BG_MAX_BLOCK 64
+typedef struct {
+  int32_t  n, ld, nblocks, nslots, ncolors, ntiles;
+  int32_t *colors;    /* [nblocks] */
+  int32_t *ctile;     /* [ncolors + 1] first tile of every colour */
+  int32_t *tile_g;    /* [ntiles] padded block width: 8, 16, 32 or 64 */
+  int32_t *tile_ew;   /* [ntiles] exterior entries per lane (the widest row of the tile) */
+  int64_t *tile_foff; /* [ntiles + 1] first factor entry, g * 64 per tile: entry j of lane l at foff + j * 64 + l */
+  int64_t *tile_eoff; /* [ntiles + 1] first exterior entry, ew * 64 per tile, laid out the same way */
+  int32_t *pos;       /* [ntiles * 64] vector position of the lane's row, -1 in lanes without a row */
+  int32_t *slot;      /* [ntiles * 64] the lane's slot blockptr[p] + i (0 in lanes without a row) */
+  double  *M, *WT;    /* [tile_foff[ntiles]] rows of W^T W and of W^T, zero outside the block */
+  double  *evals;     /* [tile_eoff[ntiles]] exterior entries in the row's storage order, then pad entries of value 0 */
+  int32_t *ecols;     /* their vector positions (pad entries: a valid position) */
+  int64_t *woff;      /* [nblocks + 1] block p's W at W + woff[p], row-major m x m */
+  double  *W, *L;     /* L (same layout) is what the factorisation left: kept for the host tests */
+  int32_t *slot_nint, *slot_next; /* [nslots] stored entries of the slot's row inside / outside its block */
+  int32_t *slot_tile_lane;        /* [nslots] tile * 64 + lane of the slot */
+  int64_t  nnz_ext;
+} pmg_bg_plan;
+/* user_colors NULL: first-fit over the blocks in block order.  pos_of_row NULL: position = row, ld = n. */
+pmg_status pmg_bg_plan_build(int32_t n, const int32_t *rowptr, const int32_t *colidx, const double *vals, int32_t nblocks, const int32_t *blockptr, const int32_t *blockrows, int32_t user_ncolors, const int32_t *user_colors, int32_t ld, const int32_t *pos_of_row, pmg_bg_plan *out);
+void       pmg_bg_plan_free(pmg_bg_plan *pl);
+/* the argument checks of pmg_blockgibbs_create_csr */
+pmg_status pmg_bg_check_blocks(int32_t n, int32_t nblocks, const int32_t *blockptr, const int32_t *blockrows);
+/* pmg_blockgibbs.c: one directional sweep over all block colours of a handle that is set up; mode as pmgk_blockgibbs_color_sweep */
+pmg_status pmg_blockgibbs_dir_sweep(pmg_blockgibbs bg, int dir, int mode, uint64_t seed, uint64_t sweep, const double *xi_slots, const double *b, double *y, void *stream);
+
 #endif

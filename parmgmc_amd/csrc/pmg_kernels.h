@@ -88,6 +88,17 @@ typedef struct {
 
 int pmgk_sell_color_sweep(const pmgk_sell *S, int slice0, int nsl, double omega, int noisy, uint64_t seed, uint64_t sweep, const double *b, double *y, void *stream);
 int pmgk_sell_residual(const pmgk_sell *S, const double *b, const double *y, double *r, void *stream);
+/* Coloured block Gibbs (kernels_blockgibbs.hip): the device copy of a pmg_bg_plan (pmg_internal.h), one wavefront per tile */
+typedef struct {
+  const int32_t *tile_g, *tile_ew;     /* [ntiles] */
+  const int64_t *tile_foff, *tile_eoff; /* [ntiles + 1] */
+  const int32_t *pos, *slot;           /* [ntiles * 64] */
+  const double  *M, *WT;               /* rows of W^T W and W^T, entry j of lane l at foff + j * 64 + l */
+  const double  *evals;                /* exterior entries, entry j of lane l at eoff + j * 64 + l */
+  const int32_t *ecols;                /* their vector positions */
+} pmgk_blockgibbs;
+/* tiles [tile0, tile0 + ntiles): the blocks of one colour.  mode 0: no noise, 1: the slot stream of (seed, sweep), 2: xi_slots */
+int pmgk_blockgibbs_color_sweep(const pmgk_blockgibbs *B, int tile0, int ntiles, int mode, uint64_t seed, uint64_t sweep, const double *xi_slots, const double *b, double *y, void *stream);
 int pmgk_permute_in(int32_t ld, const int32_t *orig, const double *nat, double *perm, void *stream);
 int pmgk_permute_out(int32_t ld, const int32_t *orig, const double *perm, double *nat, void *stream);
 

@@ -168,10 +168,23 @@ static pmg_status slab_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double
   return pmg_dist_sample_cvec(h->dist, rhs, Lv->x, 1, h->scaled, dir, seed, *ctr, ctr, stream);
 }
 
+/* `its` samples of a level smoothed by block sweeps (pmg_mgmc_set_level_blocks): the slot stream of the level's key, one draw
+   counter per directional sweep like every other level sampler.  The sweep reads the iterate outside each block, so it needs the
+   zero guess STORED: a sliced-ELL level gets it from the fill kernel or from the restriction into it (x_zeroed: every row of the
+   level is a row of P^T, the layout padding is zero since the allocation and is never written). */
+static pmg_status mg_block_sweeps(pmg_mgmc h, mg_level *Lv, int its, uint64_t seed, uint64_t *ctr, void *stream)
+{
+  pmg_sweep_iter it = pmg_sweep_begin(h->sweep_type, its, 1, *ctr);
+  while (pmg_sweep_next(&it)) PMG_CALL(pmg_blockgibbs_dir_sweep(Lv->bg, it.dir, 1, seed, it.sweep, NULL, Lv->b, Lv->x, stream));
+  *ctr = it.ctr;
+  return PMG_SUCCESS;
+}
+
 static pmg_status mg_smooth(pmg_mgmc h, int l, uint64_t seed, uint64_t *ctr, void *stream)
 {
   mg_level *Lv = &h->lv[l];
-  if (Lv->is_grid && h->dist && Lv->lrc) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, slab_dir_sweep, level_seed(seed, l), ctr, stream)); /* MATLRC on z-slabs */
+  if (Lv->bg) PMG_CALL(mg_block_sweeps(h, Lv, h->nu, level_seed(seed, l), ctr, stream));
+  else if (Lv->is_grid && h->dist && Lv->lrc) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, slab_dir_sweep, level_seed(seed, l), ctr, stream)); /* MATLRC on z-slabs */
   else if (Lv->is_grid && h->dist) PMG_CALL(pmg_dist_sample_cvec(h->dist, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* leaves the ghost planes current */
   else if (Lv->is_grid) PMG_CALL(pmg_grid_sample_cvec(Lv->g, Lv->b, Lv->x, h->nu, h->scaled, level_seed(seed, l), *ctr, ctr, stream));
   else if (Lv->is_st27) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, st27_dir_sweep, level_seed(seed, l), ctr, stream));
@@ -433,6 +446,7 @@ static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_
     mg_level *C0 = &h->lv[0];
     PMG_CALL(mg_zero_guess(C0, path[0].zero_guess, stream));
     if (h->coarse_type == 0) PMG_CALL(pmg_chol_sample(h->chol, C0->b + C0->off, C0->x + C0->off, 1, level_seed(seed, 0), ctr[0], stream));
+    else if (C0->bg) PMG_CALL(mg_block_sweeps(h, C0, h->coarse_its, level_seed(seed, 0), &ctr[0], stream));
     else if (C0->is_st27) PMG_CALL(mg_lowrank_sweeps(h, C0, h->coarse_its, st27_dir_sweep, level_seed(seed, 0), &ctr[0], stream));
     else PMG_CALL(pmg_mcsor_sample_layout(C0->mc, C0->b, C0->x, h->coarse_its, h->scaled, level_seed(seed, 0), ctr[0], &ctr[0], stream));
   }
@@ -451,6 +465,7 @@ static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_
      grid sweep (matrix-free 7-point)     24 N per directional sweep (32 N at omega != 1): read y, b, write y
      class-stencil sweep (27 x 27 table)  24 N; 16 N for the zero-guess pre-sweep of the out-of-place kernel (x not read)
      sliced-ELL sweep                     12 nnz + 40 N
+     block sweep (set_level_blocks)       pmg_blockgibbs_get_algorithmic_bytes: factors as stored + 12 nnz_ext + 28 per slot
      zero fill of a level iterate         8 N (skipped where the zero-guess sweep applies)
      grid residual + restriction fused    16 N + 8 N_c;  unfused: residual 24 N, restriction 8 N + 8 N_c
      class-stencil residual, restriction  24 N, 8 N + 8 N_c;  sliced-ELL: 12 nnz + 28 N, 12 nnz_P + 12 N_c + 8 N
@@ -478,7 +493,9 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
     /* a rank whose slab or block misses B's support launches none of the low-rank kernels: ns = 0, no bytes */
     if (p.lrc) pmg_lrc_get_sizes(p.lrc, &k, &ns, &lr_dense);
     if (lr_dense) ns = (int64_t)N; /* dense factors: every row of the level */
-    const double sweep = Lv->is_grid ? (h->omega == 1.0 ? 24.0 : 32.0) * N : (Lv->is_st27 ? 24.0 * N : 12.0 * (double)Lv->A_nnz + 40.0 * N);
+    double       bgsweep = 0.0;
+    if (Lv->bg) PMG_CALL(pmg_blockgibbs_get_algorithmic_bytes(Lv->bg, &bgsweep));
+    const double sweep = Lv->bg ? bgsweep : Lv->is_grid ? (h->omega == 1.0 ? 24.0 : 32.0) * N : (Lv->is_st27 ? 24.0 * N : 12.0 * (double)Lv->A_nnz + 40.0 * N);
     const double lrsw  = p.lrc ? ((8.0 * k + 24.0) + (16.0 * k + 24.0)) * (double)ns : 0.0;
     const double lrres = p.lrc ? (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns : 0.0; /* unrestricted residual term */
     double       by    = p.zero_guess == MG_GUESS_FILL ? 8.0 * N : (p.zero_guess == MG_GUESS_UNSET ? -8.0 * N : 0.0); /* the zero fill / the first sweep does not read x */

@@ -163,6 +163,7 @@ static pmg_status mgmc_chains_check(pmg_mgmc h, int32_t C)
 {
   PMG_CHECK(h->user_hier, PMG_ERR_SUP, "multi-chain sampling of DMDA hierarchies (pmg_mgmc_create_dmda*) is not supported: one chain already fills the device there");
   PMG_CHECK(!h->rb_dist, PMG_ERR_SUP, "multi-chain sampling of row-block distributed hierarchies is not supported");
+  PMG_CHECK(!pmg_mgmc_i_has_blocks(h), PMG_ERR_SUP, "multi-chain sampling of a hierarchy with block smoothing (pmg_mgmc_set_level_blocks) is not supported");
   PMG_CHECK(!h->lrc_k || h->is_setup, PMG_ERR_SUP, "multi-chain sampling of a hierarchy with a low-rank (MATLRC) update: whether its levels carry the update is known after pmg_mgmc_setup only");
   PMG_CHECK(h->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_mgmc_setup first");
   for (int l = 0; l < h->nlevels; ++l) {

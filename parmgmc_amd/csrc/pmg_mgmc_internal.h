@@ -62,6 +62,10 @@ typedef struct {
   hcsr          R_user; /* rows of the restriction INTO the next coarser level that this rank owns there (borrowed) */
   pmg_distmcsor dm;
   int64_t       A_nnz, P_nnz; /* stored entries of a sliced-ELL level's operator / of its CSR interpolation (traffic accounting) */
+  /* block smoothing (pmg_mgmc_set_level_blocks): copies of the caller's blocks; set-up builds `bg` from them on the level's operator,
+     in the layout of `mc`, and the level's smoothing legs then run block sweeps */
+  int32_t        bg_nblocks, bg_ncolors, *bg_blockptr, *bg_blockrows, *bg_colors;
+  pmg_blockgibbs bg;
 } mg_level;
 
 struct pmg_mgmc_s {
@@ -135,6 +139,14 @@ static inline uint64_t level_seed(uint64_t seed, int level) { return seed + 0x9E
    sweeps that later ask for them count with these two, as do the byte models */
 static inline int pmg_mgmc_i_leg_sweeps(const struct pmg_mgmc_s *h, int l) { return (l >= 1 ? h->nu : (h->coarse_type != 0 ? h->coarse_its : 0)) * pmg_sweep_ndir(h->sweep_type); }
 static inline int pmg_mgmc_i_level_sweeps(const struct pmg_mgmc_s *h, int l) { return (l >= 1 ? 2 : 1) * pmg_mgmc_i_leg_sweeps(h, l); }
+
+/* some level is smoothed by block sweeps (before set-up: is asked to be) */
+static inline int pmg_mgmc_i_has_blocks(const struct pmg_mgmc_s *h)
+{
+  for (int l = 0; l < h->nlevels; ++l)
+    if (h->lv[l].bg_blockptr) return 1;
+  return 0;
+}
 
 static inline double level_rows(const mg_level *Lv) { /* owned unknowns: a z-slab's planes, a row block's rows */ return Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n); }
 

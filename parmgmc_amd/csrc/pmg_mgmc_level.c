@@ -19,6 +19,7 @@ pmg_status pmg_mgmc_level_sweep(pmg_mgmc h, int32_t level, int backward, int noi
   mg_level *Lv;
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
   PMG_CHECK(b_lvl && x_lvl, PMG_ERR_ARG_NULL, "null vector");
+  if (Lv->bg) return pmg_blockgibbs_dir_sweep(Lv->bg, backward ? PMG_SOR_BACKWARD_SWEEP : PMG_SOR_FORWARD_SWEEP, noisy != 0, seed, counter, NULL, b_lvl, x_lvl, stream); /* the block sweep the cycle runs */
   PMG_CHECK(Lv->is_st27, PMG_ERR_SUP, "level %d: only class-stencil levels (use pmg_grid_* / pmg_mcsor_* for the others)", level);
   pmgk_st27 S = Lv->st;
   S.sqrtdiag  = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;

@@ -178,6 +178,7 @@ pmg_status pmg_mgmc_set_level_interpolation(pmg_mgmc h, int32_t level, int32_t n
 pmg_status pmg_mgmc_set_rowblock_transport(pmg_mgmc h, pmg_dist dist, const int64_t *coarse_starts)
 {
   PMG_CHECK(h && dist && coarse_starts, PMG_ERR_ARG_NULL, "null argument");
+  PMG_CHECK(!pmg_mgmc_i_has_blocks(h), PMG_ERR_SUP, "row blocks on a hierarchy with block smoothing (pmg_mgmc_set_level_blocks) are not supported");
   PMG_CHECK(h->user_hier && !h->is_setup, PMG_ERR_ARG_WRONGSTATE, "row blocks belong to pmg_mgmc_create_hierarchy, before set-up");
   int32_t rank, nranks;
   PMG_CALL(pmg_dist_get_info(dist, &rank, &nranks, NULL));
@@ -204,6 +205,7 @@ static void *dup_bytes(const void *src, size_t bytes)
 pmg_status pmg_mgmc_set_level_rowblock(pmg_mgmc h, int32_t level, int64_t row0, int32_t nowned, int32_t ncolors, const int32_t *colors_owned, const int64_t *send_ptr, const int32_t *send_idx, const int64_t *counts, const int64_t *recv_ptr, const int32_t *recv_src, const int32_t *recv_idx)
 {
   PMG_CHECK(h && colors_owned && send_ptr && counts && recv_ptr, PMG_ERR_ARG_NULL, "null argument");
+  PMG_CHECK(!pmg_mgmc_i_has_blocks(h), PMG_ERR_SUP, "row-block levels on a hierarchy with block smoothing (pmg_mgmc_set_level_blocks) are not supported");
   PMG_CHECK(h->user_hier && !h->is_setup && h->rb_dist, PMG_ERR_ARG_WRONGSTATE, "call pmg_mgmc_set_rowblock_transport first, before set-up");
   PMG_CHECK(level >= 1 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d (the coarsest level is replicated)", level);
   PMG_CHECK(row0 >= 0 && nowned >= 0 && ncolors >= 1, PMG_ERR_ARG_OUTOFRANGE, "row0 %lld, %d owned rows, %d colours", (long long)row0, nowned, ncolors);
@@ -223,6 +225,30 @@ pmg_status pmg_mgmc_set_level_rowblock(pmg_mgmc h, int32_t level, int64_t row0, 
   Lv->rb_row0    = row0;
   Lv->rb_nowned  = nowned;
   Lv->rb_ncolors = ncolors;
+  return PMG_SUCCESS;
+}
+
+/* Block Gibbs smoothing of one level of a caller-supplied hierarchy: the multiplicative patch smoother of examples/ex13.py:11-22
+   (PCASM multiplicative around -sub_pc_type cholsampler, src/pc_chols.c:174-194,220-260,284-287) as that level's smoother.
+   The blocks are copied; block_colors NULL = first-fit.  They are checked at set-up, against the level's operator. */
+pmg_status pmg_mgmc_set_level_blocks(pmg_mgmc h, int32_t level, int32_t nblocks, const int32_t *blockptr, const int32_t *blockrows, int32_t ncolors, const int32_t *block_colors)
+{
+  PMG_CHECK(h && blockptr, PMG_ERR_ARG_NULL, "null argument");
+  PMG_CHECK(h->user_hier, PMG_ERR_SUP, "block smoothing needs a caller-supplied hierarchy (pmg_mgmc_create_hierarchy): DMDA handles are not supported");
+  PMG_CHECK(!h->is_setup, PMG_ERR_ARG_WRONGSTATE, "set the blocks of a level before pmg_mgmc_setup");
+  PMG_CHECK(level >= 0 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d", level);
+  PMG_CHECK(nblocks >= 0 && (blockrows || blockptr[nblocks] == 0), PMG_ERR_ARG_OUTOFRANGE, "%d blocks", nblocks);
+  PMG_CHECK(!h->rb_dist && !h->lv[level].rb, PMG_ERR_SUP, "block smoothing of row-block distributed hierarchies is not supported");
+  PMG_CHECK(h->omega == 1.0, PMG_ERR_SUP, "block smoothing with omega = %g: a block sweep has no relaxation parameter", h->omega);
+  PMG_CHECK(!h->lrc_k, PMG_ERR_SUP, "block smoothing of a hierarchy with a low-rank update (pmg_mgmc_set_lowrank) is not supported");
+  mg_level *Lv = &h->lv[level];
+  free(Lv->bg_blockptr), free(Lv->bg_blockrows), free(Lv->bg_colors);
+  Lv->bg_blockptr  = (int32_t *)dup_bytes(blockptr, sizeof(int32_t) * ((size_t)nblocks + 1));
+  Lv->bg_blockrows = (int32_t *)dup_bytes(blockrows, sizeof(int32_t) * (size_t)(blockptr[nblocks] > 0 ? blockptr[nblocks] : 0));
+  Lv->bg_colors    = block_colors ? (int32_t *)dup_bytes(block_colors, sizeof(int32_t) * (size_t)nblocks) : NULL;
+  PMG_CHECK(Lv->bg_blockptr && Lv->bg_blockrows && (Lv->bg_colors || !block_colors), PMG_ERR_MEM, "out of host memory");
+  Lv->bg_nblocks = nblocks;
+  Lv->bg_ncolors = ncolors;
   return PMG_SUCCESS;
 }
 
@@ -275,6 +301,7 @@ pmg_status pmg_mgmc_set_smoother(pmg_mgmc h, int scaled, double omega, int sweep
   PMG_CHECK(pmg_sweep_type_ok(sweep_type), PMG_ERR_SUP, "Only forward, backward and symmetric sweep supported");
   PMG_CHECK(scaled || omega == 1.0, PMG_ERR_SUP, "sorgibbs smoothing requires omega = 1");
   PMG_CHECK(its >= 1 && (uint32_t)its * 4u <= MG_DRAWS_PER_SAMPLE, PMG_ERR_ARG_OUTOFRANGE, "smoothing iterations %d", its);
+  PMG_CHECK(omega == 1.0 || !pmg_mgmc_i_has_blocks(h), PMG_ERR_SUP, "omega = %g on a hierarchy with block smoothing: a block sweep has no relaxation parameter", omega);
   h->scaled     = scaled;
   h->omega      = omega;
   h->sweep_type = sweep_type;
@@ -337,6 +364,7 @@ pmg_status pmg_mgmc_set_lowrank(pmg_mgmc h, int32_t k, const double *B_host, con
   PMG_CHECK(h, PMG_ERR_ARG_NULL, "null handle");
   PMG_CHECK(!h->is_setup, PMG_ERR_ARG_WRONGSTATE, "set the low-rank update before pmg_mgmc_setup");
   PMG_CHECK(k >= 0 && k <= 64, PMG_ERR_ARG_OUTOFRANGE, "rank k = %d (0..64 supported)", k);
+  PMG_CHECK(k == 0 || !pmg_mgmc_i_has_blocks(h), PMG_ERR_SUP, "a low-rank update on a hierarchy with block smoothing (pmg_mgmc_set_level_blocks) is not supported");
   free(h->lrc_B);
   free(h->lrc_S);
   h->lrc_B = h->lrc_S = NULL;
@@ -601,7 +629,13 @@ static pmg_status level_make_sell(pmg_mgmc h, mg_level *Lv, const hcsr *A, int r
   PMG_CALL(pmg_mcsor_layout_len(Lv->mc, &ld32));
   Lv->ld = ld32;
   PMG_CALL(pmg_mcsor_get_layout(Lv->mc, pos));
-  return PMG_SUCCESS;
+  if (!Lv->bg_blockptr) return PMG_SUCCESS;
+  /* block smoothing: the same operator, vectors in the layout just built */
+  PMG_CHECK(h->omega == 1.0 && !h->lrc_k && !Lv->rb, PMG_ERR_SUP, "level with block smoothing: omega = 1, no low-rank update and no row block");
+  PMG_CALL(pmg_blockgibbs_create_csr(Lv->n, A->rp, A->ci, A->v, Lv->bg_nblocks, Lv->bg_blockptr, Lv->bg_blockrows, &Lv->bg));
+  if (Lv->bg_colors) PMG_CALL(pmg_blockgibbs_set_coloring(Lv->bg, Lv->bg_ncolors, Lv->bg_colors));
+  PMG_CALL(pmg_blockgibbs_set_layout(Lv->bg, ld32, pos));
+  return pmg_blockgibbs_setup(Lv->bg);
 }
 
 /* the level vectors b, x, r, the second iterate where the out-of-place sweeps want one, and the outer chain's pair in the
@@ -629,6 +663,7 @@ static pmg_status user_level_check(pmg_mgmc h, int l)
   const int top = h->nlevels - 1;
   mg_level *Lv  = &h->lv[l];
   PMG_CHECK(Lv->A_user.rp, PMG_ERR_ARG_WRONGSTATE, "level %d has no operator", l);
+  PMG_CHECK(!Lv->bg_blockptr || l >= 1 || h->coarse_type == 1, PMG_ERR_ARG_WRONG, "level 0 has blocks but is sampled exactly: block smoothing applies to a Gibbs coarse level (pmg_mgmc_set_coarse)");
   if (h->rb_dist) { /* row blocks from level rb_fold upwards; the levels below are replicated (the coarsest sampled exactly) */
     if (l == 0) {
       h->rb_fold = 1;
@@ -1021,6 +1056,8 @@ pmg_status pmg_mgmc_destroy(pmg_mgmc *hp)
     if (h->own_grid) pmg_grid_destroy(&Lv->g); /* (a slab's grid is the caller's, set up or not) */
     pmg_distmcsor_destroy(&Lv->dm);
     pmg_mcsor_destroy(&Lv->mc);
+    pmg_blockgibbs_destroy(&Lv->bg);
+    free(Lv->bg_blockptr), free(Lv->bg_blockrows), free(Lv->bg_colors);
     free(Lv->rb_colors), free(Lv->rb_send_ptr), free(Lv->rb_recv_ptr), free(Lv->rb_counts), free(Lv->rb_send_idx), free(Lv->rb_recv_src), free(Lv->rb_recv_idx);
     pmg_dev_free(Lv->b);
     pmg_dev_free(Lv->x);

@@ -311,6 +311,17 @@ class CholSampler:
             pass
 
 
+def _blocks(blocks):
+    """(nblocks, blockptr, blockrows) int32 arrays of a sequence of row lists, or of a (blockptr, blockrows) pair as is"""
+    if isinstance(blocks, tuple) and len(blocks) == 2 and isinstance(blocks[0], np.ndarray):
+        bp, br = blocks
+    else:
+        bp = np.concatenate([[0], np.cumsum([len(p) for p in blocks])])
+        br = np.concatenate([np.asarray(p, np.int64) for p in blocks]) if len(blocks) else np.zeros(0)
+    bp, br = np.ascontiguousarray(bp, np.int32), np.ascontiguousarray(br, np.int32)
+    return len(bp) - 1, bp, br
+
+
 class MGMC:
     """Multigrid Monte Carlo on a DMDA hierarchy (reference PCGAMGMC, src/pc_gamgmc.c, with -pc_gamgmc_mg_type mg)."""
 
@@ -373,6 +384,13 @@ class MGMC:
         S = np.ascontiguousarray(S, np.float64)
         assert B.ndim == 2 and B.shape[1] == len(S)
         check(lib.pmg_mgmc_set_lowrank(self._h, B.shape[1], B.ctypes.data, S.ctypes.data))
+
+    def set_level_blocks(self, level: int, blocks, block_colors=None):
+        """smooth `level` of a from_hierarchy handle with block Gibbs sweeps over `blocks` (as BlockGibbs); before setup"""
+        nb, bp, br = _blocks(blocks)
+        bc = None if block_colors is None else np.ascontiguousarray(block_colors, np.int32)
+        nc = 0 if bc is None or not len(bc) else int(bc.max()) + 1
+        check(lib.pmg_mgmc_set_level_blocks(self._h, level, nb, bp.ctypes.data, br.ctypes.data, nc, None if bc is None else bc.ctypes.data))
 
     def set_coarse(self, kind: str = "cholsampler", its: int = 1):
         check(lib.pmg_mgmc_set_coarse(self._h, {"cholsampler": 0, "gibbs": 1}[kind], its))
