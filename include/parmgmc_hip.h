@@ -783,6 +783,65 @@ pmg_status pmg_iact_chains(int64_t n, int32_t nseries, const double *X_dev, int6
    count < 2 ("Too few data points"), max_lag < 0, nacf outside [0, count]. */
 pmg_status pmg_chainstats_iact(pmg_chainstats cs, int32_t q, int32_t first, int32_t count, int32_t max_lag, double *tau_host, int32_t *window_host, int32_t *valid_host, int32_t nacf, double *acf_dev, void *stream);
 
+/* ---- Rao-Blackwellised chain statistics on the device: marginal means and variances from conditional means ------- */
+/* For x ~ N(Q^-1 b, Q^-1) every sample y gives the conditional mean of each unknown given all the others in closed form:
+       m_i = E[x_i | x_-i] = (b_i - sum_{j != i} Q_ij y_j) / Q_ii,     E[x_i] = E[m_i],     Var[x_i] = 1 / Q_ii + Var[m_i]
+   (law of total variance; the first term is exact).  The moments of m estimate the fields pmg_chainstats estimates from the
+   moments of y with less Monte Carlo error (the simple Rao-Blackwellised estimator of Siden et al. 2018) at the price of one
+   pass over the matrix per step.  One fused launch per step reads the matrix and Y (n x nchains, chain fastest, natural rows:
+   what pmg_*_sample_chains write and pmg_chains_callback receives) and merges the moments of m; m is not written to memory.
+   With a low-rank term the launches of B^T Y come first.
+   Arithmetic per row i and chain c; every product, sum and quotient is rounded on its own (no fused multiply-add):
+       s = 0.0;  s = s + a_ij * y_jc      over the STORED off-diagonal entries of row i, in stored order
+       m_ic = (b_i - s) / q_i,  q_i = a_ii                                  (one division, not a product with a reciprocal)
+   and with Q = A + B S B^T (pmg_rbstats_set_lowrank):
+       q_i = a_ii + sum_k S_k * (B_ik * B_ik)                               (k ascending, formed once on the host)
+       t = B^T y per chain                                                  (the chain kernel of the MATLRC samplers, in ITS
+                                                                             order of summation: kernels_lrc_chains.hip)
+       w = 0.0;  w = w + (B_ik * S_k) * (t_kc - B_ik * y_ic)                (k ascending)
+       m_ic = ((b_i - s) - w) / q_i
+   The moments of m_i0 .. m_i,C-1 are merged into the running (N, mean, M2) exactly as pmg_chainstats merges y (one copy of
+   that code): bm = tree sum / C, bM2 = tree sum of (m_c - bm)^2, chunks of 64 chains, Chan/Golub/LeVeque merge;
+   var = 1 / q + M2 / (N - 1) with the two quotients and the sum rounded as written.  No floating-point atomics: the order of
+   every sum is fixed by (matrix, nchains) alone, whatever the stream and the calls before (kernels_rbstats.hip).
+   Creation and all argument checks touch no device; device memory, the matrix upload included, is allocated by the first
+   update or cond_mean.  Single device; one right-hand side shared by all chains; a grid (DMDA) operator is passed as its
+   assembled CSR.  Work is enqueued on `stream` and not synchronised, except where a call returns host data or says so; the
+   first update or cond_mean after creation or after pmg_rbstats_set_lowrank allocates and uploads, which is synchronous.
+   Algorithmic bytes of one update: 12 nnz + 8 n C + 48 n (the matrix; Y once, neighbour gathers counted as cache hits; b, q,
+   mean and M2 read and written), with a low-rank term + 8 n k + 8 n C (pmg_rbstats_get_algorithmic_bytes). */
+typedef struct pmg_rbstats_s *pmg_rbstats;
+/* The matrix (host CSR, 32-bit indices, natural numbering) is copied.  PMG_ERR_ARG_OUTOFRANGE: n < 1, nchains < 1, a column
+   outside [0, n); PMG_ERR_ARG_WRONG, the code of pmg_mcsor_setup for a row without a stored diagonal entry: such a row, a
+   diagonal entry stored twice, a diagonal entry <= 0 or not finite, a rowptr that is not monotone. */
+pmg_status pmg_rbstats_create_csr(int32_t n, const int32_t *rowptr_host, const int32_t *colidx_host, const double *vals_host, int32_t nchains, pmg_rbstats *rb);
+pmg_status pmg_rbstats_destroy(pmg_rbstats *rb);
+/* Q = A + B S B^T: B is n x k column-major on the host in the matrix's row numbering, S the k diagonal entries (the arguments
+   of pmg_mcsor_set_lowrank; both copied); k = 0 removes the term.  Forgets the recorded statistics (as pmg_rbstats_reset).
+   PMG_ERR_ARG_OUTOFRANGE: k outside [0, 64]; PMG_ERR_ARG_WRONG: a q_i that is not positive and finite. */
+pmg_status pmg_rbstats_set_lowrank(pmg_rbstats rb, int32_t k, const double *B_host, const double *S_host);
+/* b: n device doubles that stay the caller's and are read by every later update / cond_mean; NULL = zero (the default) */
+pmg_status pmg_rbstats_set_rhs(pmg_rbstats rb, const double *b_dev);
+/* the stream the two callbacks below launch on (they carry none): the one the sampler is called with */
+pmg_status pmg_rbstats_set_stream(pmg_rbstats rb, void *stream);
+/* one step of all chains */
+pmg_status pmg_rbstats_update(pmg_rbstats rb, const double *Y_dev, void *stream);
+/* ready-made callbacks, ctx = the handle: pass them to pmg_mgmc_sample_chains / pmg_mgmc_sample (the latter needs nchains = 1).
+   PMG_ERR_ARG_SIZ when the sampler's sizes are not the handle's. */
+int pmg_rbstats_callback(int32_t it, const double *Y_nat_dev, int32_t n, int32_t nchains, void *ctx);
+int pmg_rbstats_sample_callback(int32_t it, const double *y_nat_dev, int32_t n, void *ctx);
+/* M_dev (n x nchains, the layout of Y_dev, another array) = the conditional means of Y_dev; records nothing */
+pmg_status pmg_rbstats_cond_mean(pmg_rbstats rb, const double *Y_dev, double *M_dev, void *stream);
+/* forget everything (the end of burn-in); waits for updates in flight */
+pmg_status pmg_rbstats_reset(pmg_rbstats rb);
+pmg_status pmg_rbstats_get_count(pmg_rbstats rb, int32_t *steps, int64_t *samples); /* samples = steps * nchains */
+/* mean = mean of m and var = 1 / q + M2 / (N - 1) of every row over all samples seen (n device doubles each; one of them may
+   be NULL).  PMG_ERR_ARG_WRONGSTATE with fewer than two samples (src/ms.c:233). */
+pmg_status pmg_rbstats_get_fields(pmg_rbstats rb, double *mean_dev, double *var_dev, void *stream);
+/* q_i = Q_ii, n host doubles */
+pmg_status pmg_rbstats_get_cond_precision(pmg_rbstats rb, double *q_host);
+pmg_status pmg_rbstats_get_algorithmic_bytes(pmg_rbstats rb, double *bytes);
+
 /* ---- covariance error over the chains on the device: the study of examples/ex6.c --------------------------------- */
 /* The ex6 consumer of pmg_*_sample_chains: EstimateCovarianceMatErrors (src/stats.c:94-117; examples/ex6.c:193) for chains
    that live on the device.  Fed one step's Y (n x nchains, chain fastest, natural rows: what pmg_chains_callback hands out),

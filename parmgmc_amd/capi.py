@@ -297,6 +297,20 @@ _sig = {
     "pmg_chainstats_rhat": (_int, [_vp, _i32, _i32, _i32, C.POINTER(_dbl)]),
     "pmg_iact_chains": (_int, [_i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pmg_chainstats_iact": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "pmg_rbstats_create_csr": (_int, [_i32, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "pmg_rbstats_destroy": (_int, [C.POINTER(_vp)]),
+    "pmg_rbstats_set_lowrank": (_int, [_vp, _i32, _vp, _vp]),
+    "pmg_rbstats_set_rhs": (_int, [_vp, _vp]),
+    "pmg_rbstats_set_stream": (_int, [_vp, _vp]),
+    "pmg_rbstats_update": (_int, [_vp, _vp, _vp]),
+    "pmg_rbstats_callback": (_int, [_i32, _vp, _i32, _i32, _vp]),
+    "pmg_rbstats_sample_callback": (_int, [_i32, _vp, _i32, _vp]),
+    "pmg_rbstats_cond_mean": (_int, [_vp, _vp, _vp, _vp]),
+    "pmg_rbstats_reset": (_int, [_vp]),
+    "pmg_rbstats_get_count": (_int, [_vp, C.POINTER(_i32), C.POINTER(_i64)]),
+    "pmg_rbstats_get_fields": (_int, [_vp, _vp, _vp, _vp]),
+    "pmg_rbstats_get_cond_precision": (_int, [_vp, _vp]),
+    "pmg_rbstats_get_algorithmic_bytes": (_int, [_vp, C.POINTER(_dbl)]),
     "pmg_chaincov_create_chol": (_int, [_vp, _i32, _i32, C.POINTER(_vp)]),
     "pmg_chaincov_create_dense": (_int, [_i32, _vp, _i32, _i32, C.POINTER(_vp)]),
     "pmg_chaincov_destroy": (_int, [C.POINTER(_vp)]),

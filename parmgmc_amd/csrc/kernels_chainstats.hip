@@ -25,6 +25,7 @@
 // No floating-point atomics anywhere; -ffp-contract=off as the rest of the library.
 #include <hip/hip_runtime.h>
 #include "pmg_kernels.h"
+#include "pmg_chain_moments.hpp"
 
 namespace {
 
@@ -40,22 +41,10 @@ inline int lpr_log2_of(int32_t C)
   return l;
 }
 
-// balanced tree over the LPR lanes of a row, neighbours first; every lane ends with the same bits
-template <int LPR>
-__device__ __forceinline__ double row_tree(double v)
-{
-#pragma unroll
-  for (int o = 1; o < LPR; o <<= 1) v = v + __shfl_xor(v, o, 64);
-  return v;
-}
-
-// (Nb, mb, Mb) merged into (N, m, M)
-__device__ __forceinline__ void merge(double N, double &m, double &M, double Nb, double mb, double Mb)
-{
-  const double d = mb - m, Np = N + Nb;
-  m = m + (d * Nb) / Np;
-  M = M + (Mb + (((d * d) * N) * Nb) / Np);
-}
+// the tree over the lane slots, the chunk moments and the merge: pmg_chain_moments.hpp, shared with kernels_rbstats.hip
+using pmg_moments::chunk_batch;
+using pmg_moments::chunk_moments;
+using pmg_moments::merge;
 
 template <int LPRL>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void chainstats_update_kernel(int64_t n, int32_t C, int nq, pmgk_chainstats_qoi Q, int iters, double N, const double *__restrict__ Y, double *__restrict__ mean, double *__restrict__ M2, double *__restrict__ partial)
@@ -108,18 +97,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void c
 #pragma unroll
       for (int i = 0; i < RW; ++i) {
         const int64_t row = rb + i * G;
-        const double  cm  = row_tree<LPR>(y[i]) / cnt;
-        const double  d   = live ? y[i] - cm : 0.0;
-        const double  cM2 = row_tree<LPR>(d * d);
-        double        bm = cm, bM2 = cM2;
-        if (LPRL == 6 && chunks > 1) { // G = 1: the wavefront's rows are it * RW + i
-          double *p = parked + ((wv * MAXRPW) + it * RW + i) * 2;
-          if (k > 0) {
-            bm = p[0], bM2 = p[1];
-            merge(seen, bm, bM2, cnt, cm, cM2);
-          }
-          if (!last && lane == 0) p[0] = bm, p[1] = bM2;
-        }
+        double        cm, cM2;
+        chunk_moments<LPR>(y[i], live, cnt, cm, cM2);
+        double bm = cm, bM2 = cM2;
+        if (LPRL == 6 && chunks > 1) // G = 1: the wavefront's rows are it * RW + i
+          chunk_batch(parked + ((wv * MAXRPW) + it * RW + i) * 2, k, last, lane, seen, cnt, cm, cM2, bm, bM2);
         if (last && cl == 0 && row < n) {
           merge(N, mo[i], vo[i], (double)C, bm, bM2);
           mean[row] = mo[i];

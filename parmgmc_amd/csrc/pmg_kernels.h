@@ -238,6 +238,23 @@ void pmgk_chainstats_geometry(int64_t n, int32_t nchains, int32_t *iters, int32_
 int  pmgk_chainstats_update(int64_t n, int32_t nchains, int nqoi, const pmgk_chainstats_qoi *Q, double count, const double *Y, double *mean, double *M2, double *partial, double *trace_step, int64_t qstride, void *stream);
 int  pmgk_chainstats_fields(int64_t n, double count, const double *mean, const double *M2, double *mean_out, double *var_out, void *stream);
 
+/* Rao-Blackwellised statistics of the chains (kernels_rbstats.hip): the conditional means m = (b - offdiag(Q) y) / diag(Q) of a
+   step's n x C array Y (chain fastest), stored (cond_mean) or merged into the running (mean, M2) as pmgk_chainstats_update
+   merges y.  The operator, all device arrays: rowptr (n + 1) / cols / vals the stored OFF-DIAGONAL entries of the rows in
+   stored order, q the n conditional precisions Q_ii, b the right-hand side (NULL: zero); k > 0: Q = A + B S B^T with B n x k
+   column-major, S the k diagonal entries and T = B^T Y (k x C, chain fastest; pmgk_lrc_btx_chains). */
+typedef struct {
+  int64_t        n;
+  const int32_t *rowptr, *cols;
+  const double  *vals, *q, *b;
+  int            k;
+  const double  *B, *S, *T;
+} pmgk_rbstats_op;
+void pmgk_rbstats_geometry(int64_t n, int32_t nchains, int32_t *iters, int32_t *nblocks);
+int  pmgk_rbstats_update(const pmgk_rbstats_op *A, int32_t nchains, double count, const double *Y, double *mean, double *M2, void *stream);
+int  pmgk_rbstats_cond_mean(const pmgk_rbstats_op *A, int32_t nchains, const double *Y, double *M, void *stream);
+int  pmgk_rbstats_fields(int64_t n, double count, const double *q, const double *mean, const double *M2, double *mean_out, double *var_out, void *stream);
+
 /* covariance over the chains (kernels_chaincov.hip): Y is n x K, k fastest; Sigma and Cout n x n row-major; partial holds
    pmgk_chaincov_ntiles(n) doubles, one per 32 x 32 tile of the lower triangle; every sum in an order that (n, K) alone fixes */
 int pmgk_chaincov_ntiles(int32_t n);

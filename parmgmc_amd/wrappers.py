@@ -468,15 +468,19 @@ class MGMC:
     def level_lowrank_residual_sub(self, level: int, x, out, restricted: bool = False):
         check(lib.pmg_mgmc_level_lowrank_residual_sub(self._h, level, int(restricted), _ptr(x), _ptr(out), _stream()))
 
-    def sample(self, b, y, its: int, seed: int, counter0: int = 0, guesszero: bool = False, callback=None, stats=None) -> int:
-        """stats: a ChainStats of one chain, updated after every sample by the library's own callback (no Python in the loop)"""
+    def sample(self, b, y, its: int, seed: int, counter0: int = 0, guesszero: bool = False, callback=None, stats=None, rb=None) -> int:
+        """stats: a ChainStats of one chain, updated after every sample by the library's own callback (no Python in the loop);
+        rb: an RBStats of one chain, the same way; both together are updated by one Python-level callback"""
         out = C.c_uint64()
-        if stats is not None:
+        if stats is not None or rb is not None:
             if callback is not None:
-                raise ValueError("stats= and callback= exclude each other")
-            cb, ctx = stats._as_callback(self.n, 1, lib.pmg_chainstats_sample_callback)
-            check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, ctx, _stream()))
-            return out.value
+                raise ValueError("stats= / rb= and callback= exclude each other")
+            if stats is not None and rb is not None:
+                callback = _update_all(self.n, 1, stats, rb)
+            else:
+                cb, ctx = stats._as_callback(self.n, 1, lib.pmg_chainstats_sample_callback) if rb is None else rb._as_callback(self.n, 1, lib.pmg_rbstats_sample_callback)
+                check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, ctx, _stream()))
+                return out.value
         if callback is None:
             cb = None
         else:
@@ -496,26 +500,29 @@ class MGMC:
         check(lib.pmg_mgmc_sample(self._h, _ptr(b), _ptr(y), its, int(guesszero), seed, counter0, C.byref(out), cb, None, _stream()))
         return out.value
 
-    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None, stats=None, cov=None) -> int:
+    def sample_chains(self, b, Y, its: int, seeds, counter0: int = 0, guesszero: bool = False, callback=None, stats=None, cov=None, rb=None) -> int:
         """`its` samples of C chains on a hierarchy from from_hierarchy: Y is a contiguous (n, C) float64 tensor, b one vector
         (n,) shared by all chains or one per chain (n, C); column c equals sample(b or b[:, c], Y[:, c], its, seeds[c], ...) bit
         for bit.  callback(it, Y) after every sample; a raised exception aborts the loop.  stats: a ChainStats(n, C) updated
         after every sample by the library's own callback instead (no Python in the loop; excludes callback).  cov: a
-        ChainCov(n, C) that records the covariance error of every sample the same way; stats= and cov= together are updated by
-        one Python-level callback.  A hierarchy with set_lowrank samples the posterior A + B diag(S) B^T the same way (after
-        setup)."""
+        ChainCov(n, C) that records the covariance error of every sample the same way; rb: an RBStats(A, C) updated the same way;
+        two or three of stats=, cov= and rb= together are updated by one Python-level callback.  A hierarchy with set_lowrank
+        samples the posterior A + B diag(S) B^T the same way (after setup)."""
         p, nc = _chains(Y, self.n)
         s = _seeds(seeds, nc)
         out = C.c_uint64()
         cb, ctx = None, None
-        if (stats is not None or cov is not None) and callback is not None:
-            raise ValueError("stats= / cov= and callback= exclude each other")
-        if stats is not None and cov is not None:
-            callback = _update_both(stats, cov, self.n, nc)
+        consumers = [x for x in (stats, cov, rb) if x is not None]
+        if consumers and callback is not None:
+            raise ValueError("stats= / cov= / rb= and callback= exclude each other")
+        if len(consumers) > 1:
+            callback = _update_all(self.n, nc, *consumers)
         elif stats is not None:
             cb, ctx = stats._as_callback(self.n, nc, lib.pmg_chainstats_callback)
         elif cov is not None:
             cb, ctx = cov._as_callback(self.n, nc)
+        elif rb is not None:
+            cb, ctx = rb._as_callback(self.n, nc, lib.pmg_rbstats_callback)
         if callback is not None:
 
             def _cb(it, ptr, n, nchains, _ctx):
@@ -596,19 +603,21 @@ class WoodburySampler:
                 callback(it, y)
         return counter0 + its
 
-    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None, stats=None, cov=None) -> int:
+    def run_chains(self, b, Y, its: int, seeds, counter0: int = 0, callback=None, sample_chains=None, stats=None, cov=None, rb=None) -> int:
         """run() on C chains of one device: Y is a contiguous (n, C) float64 tensor, b one vector (n,) shared by the chains;
         column c equals run(b, Y[:, c], its, seeds[c], counter0) bit for bit when sample_chains(W, Y, counter) advances every
         column c of Y as sample(W[:, c], Y[:, c], counter) does -- e.g. MGMC.sample_chains with per-chain right-hand sides.
-        callback(it, Y) after every sample, or stats.update(Y) for a ChainStats(n, C) and / or cov.update(Y) for a
-        ChainCov(n, C) (not both kinds)."""
+        callback(it, Y) after every sample, or stats.update(Y) for a ChainStats(n, C), cov.update(Y) for a ChainCov(n, C) and
+        rb.update(Y) for an RBStats built on (A, B, S) with this b (not both kinds)."""
         import torch
 
-        if (stats is not None or cov is not None) and callback is not None:
-            raise ValueError("stats= / cov= and callback= exclude each other")
+        if (stats is not None or cov is not None or rb is not None) and callback is not None:
+            raise ValueError("stats= / cov= / rb= and callback= exclude each other")
         p, nc = _chains(Y, self.n)
         if cov is not None:
             cov._check_sizes(self.n, nc)
+        if rb is not None:
+            rb._check_sizes(self.n, nc)
         sample_chains = sample_chains or self._sample_chains
         assert sample_chains is not None, "run_chains needs sample_chains(W, Y, counter)"
         keys = _seeds([int(v) ^ 0x5851F42D4C957F2D for v in _seeds(seeds, nc)], nc)
@@ -622,6 +631,8 @@ class WoodburySampler:
                 stats.update(Y)
             if cov is not None:
                 cov.update(Y)
+            if rb is not None:
+                rb.update(Y)
             if callback is not None:
                 callback(it, Y)
         return counter0 + its
@@ -819,16 +830,16 @@ class ChainCov:
             pass
 
 
-def _update_both(stats, cov, n: int, nchains: int):
-    """a Python-level chains callback that feeds a ChainStats and a ChainCov of the sampler's sizes"""
-    assert (n, nchains) == (stats.n, stats.nchains), f"ChainStats of {stats.n} x {stats.nchains} on samples of {n} x {nchains}"
-    cov._check_sizes(n, nchains)
+def _update_all(n: int, nchains: int, *consumers):
+    """a Python-level callback that feeds several of ChainStats, ChainCov and RBStats of the sampler's sizes, in the order given"""
+    for x in consumers:
+        assert (n, nchains) == (x.n, x.nchains), f"{type(x).__name__} of {x.n} x {x.nchains} on samples of {n} x {nchains}"
 
-    def both(it, Y):
-        stats.update(Y)
-        cov.update(Y)
+    def update_all(it, Y):
+        for x in consumers:
+            x.update(Y)
 
-    return both
+    return update_all
 
 
 def gelman_rubin(vals) -> float:
@@ -918,3 +929,6 @@ def make_observation_mats(nx, ny, nz, coords, radii, obsvals, sigma2, kz0=0, nz_
     S, f = np.zeros(k), np.zeros(n)
     check(lib.pmg_make_observation_mats_dmda(nx, ny, nz, kz0, nz_owned, k, sigma2, coords.ctypes.data, radii.ctypes.data, vals.ctypes.data, B.ctypes.data, S.ctypes.data, f.ctypes.data))
     return B, S, f
+
+
+from .rbstats import RBStats  # noqa: E402,F401  (its own module; needs _ptr and _stream above)

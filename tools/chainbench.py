@@ -21,6 +21,11 @@ MGMC call), each beside its single-chain entry point (mcsor sample; the Woodbury
 the hierarchy that carries the update on every level (MGMC.set_lowrank; mg.sample beside mg.sample_chains), one cycle per sample
 as the Woodbury line, with its ratio to that line.  --matlrc-only: only the MATLRC MGMC chains calls (for runs under rocprofv3).
 
+--rb: the Rao-Blackwellised statistics instead (pmg_rbstats_update on the fine operator with b): time per update on an (n, C)
+array, its algorithmic bytes 12 nnz + 8 n C + 48 n over that time, pmg_chainstats_update (no QOI) on the same Y in the same run,
+the triad on the update's bytes and on those of one chains residual pass (12 nnz + 16 n C + 8 n); then MGMC chains plain, with
+stats= and with rb=.
+
 --cov: the covariance-error lines instead (pmg_chaincov_update; the config-4 mesh is not built): for n in {1024, 4096} x C in
 {32, 1000}, time per update (median of `regions` event-timed groups of 20 updates), n (n + 1) C flops over that time against the
 78.6 TFLOP/s f64 matrix peak of the vendor's data sheet, and at n = 1024 the host path on the same data: the device -> host copy of Y
@@ -71,6 +76,7 @@ def main():
     ap.add_argument("--stats", action="store_true", help="the chain-statistics lines (pmg_chainstats_update)")
     ap.add_argument("--iact", action="store_true", help="with --stats: the IACT of every chain on the device beside the host path, effective samples per second")
     ap.add_argument("--iact-steps", type=int, default=1000, help="with --iact: steps of the MGMC chains call whose trace is analysed")
+    ap.add_argument("--rb", action="store_true", help="the Rao-Blackwellised statistics lines (pmg_rbstats_update beside pmg_chainstats_update on the same Y)")
     ap.add_argument("--cov", action="store_true", help="the covariance-error lines (pmg_chaincov_update)")
     ap.add_argument("--cov-updates-only", action="store_true", help="with --cov: only the update groups (for runs under rocprofv3)")
     args = ap.parse_args()
@@ -102,6 +108,8 @@ def main():
     its = args.its
     if args.stats:
         return stats_lines(args, n, mg, b)
+    if args.rb:
+        return rb_lines(args, A, mc, mg, b)
     if args.lowrank:
         return lowrank_lines(args, xy, A, mg, b, ops, ps)
     if args.sweep_only:
@@ -225,6 +233,76 @@ def stats_lines(args, n, mg, b):
         torch.cuda.empty_cache()
     if args.iact:
         iact_lines(args, n, mg, b, w)
+
+
+def rb_lines(args, A, mc, mg, b):
+    """pmg_rbstats_update on the fine operator: time per update (median of `regions` event-timed groups of 20 updates) beside
+    pmg_chainstats_update on the same Y in the same run, the read-2/write-1 triad on the update's algorithmic bytes
+    (12 nnz + 8 n C + 48 n) and on those of one chains residual pass (12 nnz + 16 n C + 8 n: the library has no entry point that
+    runs that pass alone; the Gibbs sweep, which walks the same rows with the same gathers, is timed beside it), then the MGMC
+    chains call with and without rb="""
+    import torch
+
+    from parmgmc_amd import ChainStats, RBStats
+    from parmgmc_amd.capi import check, lib
+
+    reps = 20
+    n, nnz = A.shape[0], A.nnz
+    gen = torch.Generator(device="cuda").manual_seed(1)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def triad_us(nbytes):
+        nt = int(nbytes / 24.0) & ~1
+        a3, b3, c3 = (torch.zeros(nt, dtype=torch.float64, device="cuda") for _ in range(3))
+
+        def triad():
+            for _ in range(reps):
+                check(lib.pmg_stream_triad(nt, a3.data_ptr(), b3.data_ptr(), c3.data_ptr(), st))
+
+        return timed(triad, args.regions) / reps * 1e3
+
+    for C in args.chains:
+        Y = torch.randn((n, C), dtype=torch.float64, device="cuda", generator=gen)
+        rb = RBStats(A, C, b=b)
+        cs = ChainStats(n, C, [], max_steps=reps * (args.regions + 1))
+
+        def rb_updates():
+            for _ in range(reps):
+                rb.update(Y)
+
+        def cs_updates():
+            for _ in range(reps):
+                cs.update(Y)
+
+        us_rb = timed(rb_updates, args.regions) / reps * 1e3
+        us_cs = timed(cs_updates, args.regions) / reps * 1e3
+        alg = rb.algorithmic_bytes()
+        assert alg == 12.0 * nnz + 8.0 * n * C + 48.0 * n
+        us_triad = triad_us(alg)
+        us_resid = triad_us(12.0 * nnz + 16.0 * n * C + 8.0 * n)
+        Ys = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+        us_sweep = timed(lambda: mc.sample_chains(b, Ys, args.its, [0xCAFE + 7919 * c for c in range(C)]), args.regions) / args.its * 1e3
+        mean, var = rb.fields()
+        rec = {"chains": C, "rb_update_us": us_rb, "algorithmic_bytes": alg, "rb_update_GBps": alg / us_rb / 1e3, "chainstats_update_us": us_cs, "triad_us_same_bytes": us_triad,
+               "rb_over_triad_time": us_rb / us_triad, "triad_us_residual_bytes": us_resid, "rb_over_chainstats_plus_residual_triad": us_rb / (us_cs + us_resid), "gibbs_sweep_us": us_sweep,
+               "finite": bool(torch.isfinite(mean).all().item() and torch.isfinite(var).all().item())}
+        print(json.dumps(rec), flush=True)
+        del Y, Ys, rb, cs
+        torch.cuda.empty_cache()
+    its = args.its
+    for C in args.chains:
+        seeds = [0xCAFE + 7919 * c for c in range(C)]
+        Y = torch.zeros((n, C), dtype=torch.float64, device="cuda")
+        rb = RBStats(A, C, b=b)
+        cs = ChainStats(n, C, [], max_steps=its * (args.regions + 1))
+        plain = timed_all(lambda: mg.sample_chains(b, Y, its, seeds), args.regions)
+        with_stats = timed_all(lambda: mg.sample_chains(b, Y, its, seeds, stats=cs), args.regions)
+        with_rb = timed_all(lambda: mg.sample_chains(b, Y, its, seeds, rb=rb), args.regions)
+        print(json.dumps({"chains": C, "its": its, "mgmc_ms_per_sample": plain[0] / its, "mgmc_stats_ms_per_sample": with_stats[0] / its, "mgmc_rb_ms_per_sample": with_rb[0] / its,
+                          "mgmc_rb_spread_ms_per_sample": [with_rb[1] / its, with_rb[2] / its], "rb_added_us_per_sample": (with_rb[0] - plain[0]) / its * 1e3,
+                          "stats_added_us_per_sample": (with_stats[0] - plain[0]) / its * 1e3, "steps_recorded": rb.count()[0]}), flush=True)
+        del Y, rb, cs
+        torch.cuda.empty_cache()
 
 
 def wall_ms(fn, regions):
