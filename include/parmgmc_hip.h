@@ -232,6 +232,8 @@ pmg_status pmg_blockgibbs_sweep_xi(pmg_blockgibbs bg, int backward, const double
 /* bytes one noisy directional sweep needs: the factors as stored (rows of W^T W and of W^T, padded to the tile), 12 per
    exterior entry, per slot 4 (position) + 8 (b) + 8 (y read) + 8 (y written) */
 pmg_status pmg_blockgibbs_get_algorithmic_bytes(pmg_blockgibbs bg, double *bytes);
+/* many chains per launch: pmg_blockgibbs_apply_chains, _sample_chains, _sample_chains_rhs, _sweep_xi_chains below, after
+   pmg_chains_callback */
 pmg_status pmg_blockgibbs_destroy(pmg_blockgibbs *bg);
 
 /* ------------------------------------------------------------------------------------------------------ */
@@ -540,6 +542,30 @@ pmg_status pmg_mgmc_sample_chains_rhs(pmg_mgmc mg, int32_t nchains, const uint64
    operands (matrices, idiag, sqrtdiag, the shared b, P, W, the low-rank factors and their rows) counted once, iterates, k-vectors
    and per-chain right-hand sides C times; the formula is listed at the definition (pmg_mgmc_chains.c) and in DESIGN.md 11.1 */
 pmg_status pmg_mgmc_get_algorithmic_bytes_chains(pmg_mgmc mg, int32_t nchains, double *total, double *per_level_host);
+/* pmg_blockgibbs_apply / _sample / _sweep_xi on C CHAINS of one operator (examples/ex13.py runs this sampler where many chains
+   are wanted, an IACT and covariance study of the squared operator): one launch per block colour advances all of them, and the
+   per-block factors, the exterior entries and the launches are paid once for C chains.  Y is len x nchains doubles on the
+   device, chain fastest (Y[i * nchains + c]), with len and i the handle's own indexing: row and n, or position and ld after
+   pmg_blockgibbs_set_layout -- the indexing of pmg_blockgibbs_apply, so nothing is permuted and no iterate workspace exists; the
+   only per-object state is the device copy of the seeds.  b is ONE vector of len entries shared by the chains; B_dev of _rhs is
+   len x nchains, Xi_slots_dev nslots x nchains, both chain fastest.  Column c after the call equals, bit for bit,
+   pmg_blockgibbs_apply / pmg_blockgibbs_sample / pmg_blockgibbs_sweep_xi on that column alone with seed = seeds_host[c], the same
+   counter0, the handle's sweep type, and b or B[:, c] (Xi[:, c]); *counter_out is the single-chain value.  Rows in no block and
+   positions outside the layout's image are never written in any column.  cb (may be NULL) is called after every sample with
+   (it, Y_dev, len, nchains, cbctx), the sample valid in stream order; a non-zero return aborts the call with that status
+   (pmg_chainstats_callback and pmg_rbstats_callback fit).  Checks, before any device work and in this order: PMG_ERR_ARG_NULL (NULL
+   handle, seeds, b or Y), PMG_ERR_ARG_OUTOFRANGE (nchains < 1, its < 0, sizes beyond 64-bit / launch limits),
+   PMG_ERR_ARG_WRONGSTATE (not set up).  Replacing the seeds or growing their buffer synchronises `stream`; with the seeds of the
+   previous call nothing does. */
+pmg_status pmg_blockgibbs_apply_chains(pmg_blockgibbs bg, int32_t nchains, const double *b_dev, double *Y_dev, void *stream);
+pmg_status pmg_blockgibbs_sample_chains(pmg_blockgibbs bg, int32_t nchains, const uint64_t *seeds_host, const double *b_dev, double *Y_dev, int32_t its, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
+pmg_status pmg_blockgibbs_sample_chains_rhs(pmg_blockgibbs bg, int32_t nchains, const uint64_t *seeds_host, const double *B_dev, double *Y_dev, int32_t its, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream);
+/* diagnostic: ONE directional sweep of every chain with the normals read from Xi_slots_dev */
+pmg_status pmg_blockgibbs_sweep_xi_chains(pmg_blockgibbs bg, int32_t nchains, int backward, const double *Xi_slots_dev, const double *b_dev, double *Y_dev, void *stream);
+/* bytes of one noisy directional sweep of C chains, shared operands once (the convention of pmg_mgmc_get_algorithmic_bytes_chains):
+   the factors and 12 per exterior entry as pmg_blockgibbs_get_algorithmic_bytes, per slot 4 (position) + 8 (shared b; 8 C with
+   per_chain_rhs != 0) + 16 C (y read and written).  nchains = 1 with a shared b is pmg_blockgibbs_get_algorithmic_bytes. */
+pmg_status pmg_blockgibbs_get_algorithmic_bytes_chains(pmg_blockgibbs bg, int32_t nchains, int per_chain_rhs, double *bytes);
 /* Diagnostics: ONE kernel of the V-cycle on caller-supplied device vectors in the level's own layout (single device).
    They exist for the parity tests at 257^3 / 513^3, where a whole oracle cycle is out of reach: the tests run one
    kernel and compare sampled rows with the oracle's row arithmetic (PCMG pieces entered at reference

@@ -336,6 +336,11 @@ _sig = {
     "pmg_blockgibbs_sample": (_int, [_vp, _vp, _vp, _i32, _u64, _u64, C.POINTER(_u64), _vp]),
     "pmg_blockgibbs_sweep_xi": (_int, [_vp, _int, _vp, _vp, _vp, _vp]),
     "pmg_blockgibbs_get_algorithmic_bytes": (_int, [_vp, C.POINTER(_dbl)]),
+    "pmg_blockgibbs_apply_chains": (_int, [_vp, _i32, _vp, _vp, _vp]),
+    "pmg_blockgibbs_sample_chains": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
+    "pmg_blockgibbs_sample_chains_rhs": (_int, [_vp, _i32, _vp, _vp, _vp, _i32, _u64, C.POINTER(_u64), _vp, _vp, _vp]),
+    "pmg_blockgibbs_sweep_xi_chains": (_int, [_vp, _i32, _int, _vp, _vp, _vp, _vp]),
+    "pmg_blockgibbs_get_algorithmic_bytes_chains": (_int, [_vp, _i32, _int, C.POINTER(_dbl)]),
     "pmg_blockgibbs_destroy": (_int, [C.POINTER(_vp)]),
     "pmg_mgmc_set_level_blocks": (_int, [_vp, _i32, _i32, _vp, _vp, _i32, _vp]),
 }

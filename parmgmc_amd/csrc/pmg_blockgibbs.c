@@ -21,6 +21,7 @@ struct pmg_blockgibbs_s {
   pmg_bg_plan     plan; /* host: colours, tile ranges, W; the packed arrays are freed once they are on the device */
   pmgk_blockgibbs K;    /* device */
   double          bytes;
+  pmg_keybuf      ch_keys; /* the noise keys of the last chains call: the only per-object state of the chains entry points */
 };
 
 #define BG_SETUP(bg) PMG_CHECK((bg)->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_blockgibbs_setup first")
@@ -228,9 +229,92 @@ pmg_status pmg_blockgibbs_sweep_xi(pmg_blockgibbs bg, int backward, const double
   return pmg_blockgibbs_dir_sweep(bg, backward ? PMG_SOR_BACKWARD_SWEEP : PMG_SOR_FORWARD_SWEEP, 2, 0, 0, xi_slots, b, y, stream);
 }
 
+/* ---- many chains per launch -------------------------------------------------------------------------------------------
+   Y is len x C doubles, chain fastest, in the handle's own indexing (rows, or positions after pmg_blockgibbs_set_layout): the
+   vectors are in their layout already, so there is no permutation and no iterate workspace.  One launch per block colour
+   sweeps every chain (kernels_blockgibbs_chains.hip); column c follows the single-chain path with key keys[c]. */
+
+static int64_t bg_len(pmg_blockgibbs bg) { return bg->pos_of_row ? bg->ld : bg->n; }
+
+/* one direction over all block colours on C chains; mode as pmgk_blockgibbs_color_sweep, bcs = chain stride of b (0 | 1) */
+pmg_status pmg_blockgibbs_dir_sweep_chains(pmg_blockgibbs bg, int dir, int mode, int32_t C, const uint64_t *keys_dev, uint64_t sweep, const double *Xi, const double *b, int bcs, double *Y, void *stream)
+{
+  const pmg_bg_plan *pl = &bg->plan;
+  int                rc = 0;
+  for (int32_t cc = 0; cc < pl->ncolors && !rc; ++cc) {
+    const int32_t c = pmg_sweep_color(dir, pl->ncolors, cc);
+    rc = pmgk_blockgibbs_color_sweep_chains(&bg->K, pl->ctile[c], pl->ctile[c + 1] - pl->ctile[c], mode, C, keys_dev, sweep, Xi, b, bcs, Y, stream);
+  }
+  PMG_KERNEL(rc);
+  return PMG_SUCCESS;
+}
+
+/* the checks of every chains entry point, before any device work: NULL, ranges, sizes, state -- in this order */
+static pmg_status bg_chains_args(pmg_blockgibbs bg, int32_t C, int need_seeds, const uint64_t *seeds, const void *xi, int need_xi, const double *b, const double *Y, int32_t its)
+{
+  PMG_CHECK(bg, PMG_ERR_ARG_NULL, "null block Gibbs handle");
+  PMG_CHECK(b && Y && (seeds || !need_seeds) && (xi || !need_xi || (bg->is_setup && !bg->plan.nslots)), PMG_ERR_ARG_NULL, "null argument");
+  PMG_CHECK(C >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", C);
+  PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
+  PMG_CALL(pmg_chains_size_check(bg_len(bg), C));
+  BG_SETUP(bg);
+  return PMG_SUCCESS;
+}
+
+static pmg_status bg_chains_run(pmg_blockgibbs bg, int32_t C, const uint64_t *seeds, int noisy, const double *b, int bcs, double *Y, int32_t its, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+{
+  PMG_CALL(bg_chains_args(bg, C, noisy, seeds, NULL, 0, b, Y, its));
+  if (noisy) PMG_CALL(pmg_keybuf_set(&bg->ch_keys, seeds, C, stream));
+  const int      ndir = pmg_sweep_ndir(bg->type);
+  pmg_sweep_iter it   = pmg_sweep_begin(bg->type, its, noisy, counter0);
+  while (pmg_sweep_next(&it)) {
+    PMG_CALL(pmg_blockgibbs_dir_sweep_chains(bg, it.dir, noisy, C, noisy ? bg->ch_keys.dev : NULL, it.sweep, NULL, b, bcs, Y, stream));
+    if (cb && (it.index + 1) % ndir == 0) { /* a sample is complete */
+      const int rc = cb((int32_t)(it.index / ndir), Y, (int32_t)bg_len(bg), C, cbctx);
+      PMG_CHECK(rc == 0, rc, "sample callback returned %d", rc);
+    }
+  }
+  if (counter_out) *counter_out = it.ctr;
+  return PMG_SUCCESS;
+}
+
+pmg_status pmg_blockgibbs_apply_chains(pmg_blockgibbs bg, int32_t nchains, const double *b, double *Y, void *stream)
+{
+  return bg_chains_run(bg, nchains, NULL, 0, b, 0, Y, 1, 0, NULL, NULL, NULL, stream);
+}
+
+pmg_status pmg_blockgibbs_sample_chains(pmg_blockgibbs bg, int32_t nchains, const uint64_t *seeds, const double *b, double *Y, int32_t its, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+{
+  return bg_chains_run(bg, nchains, seeds, 1, b, 0, Y, its, counter0, counter_out, cb, cbctx, stream);
+}
+
+pmg_status pmg_blockgibbs_sample_chains_rhs(pmg_blockgibbs bg, int32_t nchains, const uint64_t *seeds, const double *B, double *Y, int32_t its, uint64_t counter0, uint64_t *counter_out, pmg_chains_callback cb, void *cbctx, void *stream)
+{
+  return bg_chains_run(bg, nchains, seeds, 1, B, 1, Y, its, counter0, counter_out, cb, cbctx, stream);
+}
+
+pmg_status pmg_blockgibbs_sweep_xi_chains(pmg_blockgibbs bg, int32_t nchains, int backward, const double *Xi_slots, const double *b, double *Y, void *stream)
+{
+  PMG_CALL(bg_chains_args(bg, nchains, 0, NULL, Xi_slots, 1, b, Y, 0));
+  return pmg_blockgibbs_dir_sweep_chains(bg, backward ? PMG_SOR_BACKWARD_SWEEP : PMG_SOR_FORWARD_SWEEP, 2, nchains, NULL, 0, Xi_slots, b, 0, Y, stream);
+}
+
+/* one noisy directional sweep on C chains; operands every chain shares (factors, exterior entries, positions, a shared b) count once */
+pmg_status pmg_blockgibbs_get_algorithmic_bytes_chains(pmg_blockgibbs bg, int32_t nchains, int per_chain_rhs, double *bytes)
+{
+  PMG_CHECK(bg && bytes, PMG_ERR_ARG_NULL, "null argument");
+  PMG_CHECK(nchains >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", nchains);
+  BG_SETUP(bg);
+  const pmg_bg_plan *pl = &bg->plan;
+  const double       ns = (double)pl->nslots, C = (double)nchains;
+  *bytes = 2.0 * 8.0 * (double)pl->tile_foff[pl->ntiles] + 12.0 * (double)pl->nnz_ext + 4.0 * ns + 8.0 * ns * (per_chain_rhs ? C : 1.0) + 16.0 * ns * C;
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_blockgibbs_destroy(pmg_blockgibbs *bg)
 {
   if (!bg || !*bg) return PMG_SUCCESS;
+  pmg_keybuf_free(&(*bg)->ch_keys);
   bg_free_device(*bg);
   pmg_bg_plan_free(&(*bg)->plan);
   free((*bg)->blockptr), free((*bg)->blockrows), free((*bg)->user_colors), free((*bg)->pos_of_row);

@@ -209,5 +209,8 @@ void       pmg_bg_plan_free(pmg_bg_plan *pl);
 pmg_status pmg_bg_check_blocks(int32_t n, int32_t nblocks, const int32_t *blockptr, const int32_t *blockrows);
 /* pmg_blockgibbs.c: one directional sweep over all block colours of a handle that is set up; mode as pmgk_blockgibbs_color_sweep */
 pmg_status pmg_blockgibbs_dir_sweep(pmg_blockgibbs bg, int dir, int mode, uint64_t seed, uint64_t sweep, const double *xi_slots, const double *b, double *y, void *stream);
+/* the same on C chains: vectors in the handle's layout, len x C, chain fastest; keys on the device (mode 1), Xi nslots x C (mode 2),
+   bcs = chain stride of b (0: one shared vector, 1: len x C).  What a chains V-cycle would call on a block level. */
+pmg_status pmg_blockgibbs_dir_sweep_chains(pmg_blockgibbs bg, int dir, int mode, int32_t C, const uint64_t *keys_dev, uint64_t sweep, const double *Xi, const double *b, int bcs, double *Y, void *stream);
 
 #endif

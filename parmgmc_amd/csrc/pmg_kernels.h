@@ -99,6 +99,9 @@ typedef struct {
 } pmgk_blockgibbs;
 /* tiles [tile0, tile0 + ntiles): the blocks of one colour.  mode 0: no noise, 1: the slot stream of (seed, sweep), 2: xi_slots */
 int pmgk_blockgibbs_color_sweep(const pmgk_blockgibbs *B, int tile0, int ntiles, int mode, uint64_t seed, uint64_t sweep, const double *xi_slots, const double *b, double *y, void *stream);
+/* the same on C chains (kernels_blockgibbs_chains.hip): vectors len x C, chain fastest; mode 1 draws chain c with key keys_dev[c],
+   mode 2 reads Xi_slots[slot * C + c]; bcs = chain stride of b (0: one shared vector, 1: len x C) */
+int pmgk_blockgibbs_color_sweep_chains(const pmgk_blockgibbs *B, int tile0, int ntiles, int mode, int32_t C, const uint64_t *keys_dev, uint64_t sweep, const double *Xi_slots, const double *b, int bcs, double *Y, void *stream);
 int pmgk_permute_in(int32_t ld, const int32_t *orig, const double *nat, double *perm, void *stream);
 int pmgk_permute_out(int32_t ld, const int32_t *orig, const double *perm, double *nat, void *stream);
 

@@ -8,11 +8,16 @@
 Per operator one JSON line: ms per forward directional sweep of both samplers (device events around `--reps` noisy sweeps after
 a warm-up), the byte model of a sweep and the fraction of 8 TB/s it gives at that time, and with --iact the integrated
 autocorrelation time of one ball quantity of interest over 32 chains x 4000 steps (pmg_iact_chains, the reference's window rule)
-with the time per effective sample = IACT x ms per sweep.  The chains are deterministic in their seeds, so the IACT part needs
-one run; the timings are taken from fresh processes (tools/blockbench.py grid; tools/blockbench.py lshape; ...)."""
+with the time per effective sample = IACT x ms per sweep.  --chains C1,C2,... (default 1,8,32,128) adds, per C, the block sampler
+advancing C chains per launch (pmg_blockgibbs_sample_chains) under the same protocol: ms per noisy forward sweep of all chains,
+chain-sweeps per second, the chains byte model and its fraction of 8 TB/s, next to the single-chain line (DESIGN.md section
+12.1); --chains "" leaves it out.  The chains are deterministic in their seeds, so the IACT part needs one run (both samplers
+advance all 32 chains per launch); the timings are taken from fresh processes (tools/blockbench.py grid; tools/blockbench.py
+lshape; ...)."""
 import argparse
 import json
 import sys
+import time
 from pathlib import Path
 
 import numpy as np
@@ -22,7 +27,7 @@ ROOT = Path(__file__).resolve().parent.parent
 sys.path.insert(0, str(ROOT))
 import torch
 
-from parmgmc_amd import MCSOR, BlockGibbs, iact_chains
+from parmgmc_amd import MCSOR, BlockGibbs, ChainStats, iact_chains
 from parmgmc_amd.unstructured import assemble_p1, ball_observations, greedy_aggregation, read_gmsh41_triangles, refine_uniform
 
 PEAK = 8e12  # bytes per second
@@ -73,6 +78,7 @@ def main():
     ap.add_argument("--reps", type=int, default=400)
     ap.add_argument("--iact", action="store_true")
     ap.add_argument("--steps", type=int, default=STEPS)
+    ap.add_argument("--chains", default="1,8,32,128", help="chain counts of the block sampler's chains form, comma separated")
     a = ap.parse_args()
     A, blocks, w = grid_case(a.n, a.shift) if a.case == "grid" else lshape_case(a.refine, a.kappa)
     n, nnz = A.shape[0], A.nnz
@@ -88,6 +94,16 @@ def main():
     out["block_bytes"], out["point_bytes"] = bg.algorithmic_bytes(), 12.0 * nnz + 40.0 * n
     for k in ("block", "point"):
         out[f"{k}_fraction_of_8TBs"] = out[f"{k}_bytes"] / (out[f"{k}_ms_per_sweep"] * 1e-3) / PEAK
+    out["block_chain_sweeps_per_s"] = 1e3 / out["block_ms_per_sweep"]
+    out["block_chains"] = []
+    for nc in [int(v) for v in a.chains.split(",") if v]:
+        Yc = torch.zeros(n, nc, dtype=torch.float64, device="cuda")
+        seeds = list(range(1, 1 + nc))
+        ms = timed(lambda its, c0: bg.sample_chains(b, Yc, its, seeds, counter0=c0), a.reps)
+        nbytes = bg.algorithmic_bytes_chains(nc)
+        out["block_chains"].append(dict(chains=nc, ms_per_sweep=ms, chain_sweeps_per_s=nc * 1e3 / ms, bytes=nbytes, fraction_of_8TBs=nbytes / (ms * 1e-3) / PEAK,
+                                        speedup_over_single_chain=nc * out["block_ms_per_sweep"] / ms))
+        del Yc
     if a.iact:
         wd = torch.as_tensor(w, device="cuda")
         X = torch.empty(a.steps, CHAINS, dtype=torch.float64, device="cuda")
@@ -100,12 +116,16 @@ def main():
             torch.matmul(wd, Y, out=X[s])
         tau, _, valid = iact_chains(X)
         out["point_iact"] = dict(median=float(np.median(tau)), min=float(tau.min()), max=float(tau.max()), valid=int(valid.sum()))
-        for c in range(CHAINS):  # block Gibbs: chain after chain
-            y.zero_()
-            for s in range(a.steps):
-                bg.sample(b, y, 1, seed=seeds[c], counter0=s)
-                torch.dot(wd, y, out=X[s, c])
-        tau, _, valid = iact_chains(X)
+        # block Gibbs: all chains per launch, one call for all steps; column c is the chain bg.sample(seed=seeds[c]) gives, and the
+        # library's own callback records w . Y[:, c] of every step on the device (no Python in the loop)
+        cs = ChainStats(n, CHAINS, qois=[w], max_steps=a.steps)
+        Y.zero_()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        bg.sample_chains(b, Y, a.steps, seeds, counter0=0, stats=cs)
+        torch.cuda.synchronize()
+        out["block_iact_wall_s"] = time.perf_counter() - t0
+        tau, _, valid = cs.iact_device(0)
         out["block_iact"] = dict(median=float(np.median(tau)), min=float(tau.min()), max=float(tau.max()), valid=int(valid.sum()))
         for k in ("block", "point"):
             out[f"{k}_ms_per_effective_sample"] = out[f"{k}_iact"]["median"] * out[f"{k}_ms_per_sweep"]
