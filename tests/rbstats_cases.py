@@ -44,6 +44,9 @@ EPS = np.finfo(np.float64).eps
 # every lpr (9 and 17 are there for the splits of 16 and 32 lanes per row), a partial last lane group, the chunk boundary, a
 # partial last chunk
 CHAINS = [1, 2, 3, 5, 8, 9, 17, 33, 64, 65, 130]
+# the full lane groups of 4, 16 and 32 lanes per row, one chain short of a full chunk, and the second chunk edge: two full chunks |
+# three chunks with a last chunk of one chain
+MORE_CHAINS = [4, 16, 32, 63, 128, 129]
 RANKS = [0, 1, 3, 5]  # pmg_mcsor_set_lowrank's chain path takes k <= 64: 5 is the rank above 3
 WIDE = 70  # stored entries of the wide row: more than one wavefront of lanes at lpr = 1
 

@@ -34,11 +34,11 @@ INTEGER = {M.name: M for M in R.integer_matrices()}
 
 
 # ---- 1: cond_mean over the case table -----------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C_", R.CHAINS)
+@pytest.mark.parametrize("C_", R.CHAINS + R.MORE_CHAINS)
 @pytest.mark.parametrize("name", list(MATRICES))
 def test_cond_mean_against_longdouble(name, C_):
     """every rank of the table on one handle, with and without a right-hand side.
-    Observed on the MI355X: worst |m - ref| / bound over the whole table 0.29 (k = 0), 0.17 (k > 0)."""
+    Observed on the MI355X: worst |m - ref| / bound over the whole table 0.29 (k = 0), 0.18 (k > 0)."""
     M = MATRICES[name]
     Y = R.samples(M.n, C_, seed=M.n + C_)
     b = R.rhs(M.n, seed=C_)
@@ -59,7 +59,7 @@ def test_cond_mean_against_longdouble(name, C_):
     assert rb.count() == (0, 0)  # cond_mean records nothing
 
 
-@pytest.mark.parametrize("C_", R.CHAINS)
+@pytest.mark.parametrize("C_", R.CHAINS + R.MORE_CHAINS)
 @pytest.mark.parametrize("name", list(INTEGER))
 def test_cond_mean_exact_on_integer_data(name, C_):
     """k = 0, integer off-diagonal entries, y and b, power-of-two diagonal: no operation rounds, the result is the exact one"""
@@ -75,7 +75,7 @@ def test_cond_mean_exact_on_integer_data(name, C_):
 
 
 # ---- 2: a diagonal Q ----------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C_", R.CHAINS)
+@pytest.mark.parametrize("C_", R.CHAINS + R.MORE_CHAINS)
 def test_diagonal_matrix(C_):
     """m = b / q for every sample: mean == b / q, M2 == 0 and var == 1 / q bit for bit after 1, 2 and 5 updates.  The mean of C
     equal values is formed as (tree sum) / C, which returns the value bit for bit when C x is exact: dyadic data (integer b,
@@ -84,7 +84,7 @@ def test_diagonal_matrix(C_):
 
     n = 67
     for dyadic in (True, False):
-        if not dyadic and C_ not in (1, 2, 8, 64, 65, 130):
+        if not dyadic and C_ not in (1, 2, 8, 64, 65, 130, 4, 16, 32, 128):
             continue
         M = R.diagonal(n, seed=C_, dyadic=dyadic)
         b = R.rhs(n, seed=C_, integer=dyadic)
@@ -149,7 +149,7 @@ def test_order_contract_against_chainstats(name, C_, k):
 
 
 # ---- 4: the fields against np.longdouble --------------------------------------------------------------------------------------
-@pytest.mark.parametrize("C_", R.CHAINS)
+@pytest.mark.parametrize("C_", R.CHAINS + R.MORE_CHAINS)
 @pytest.mark.parametrize("name,k", [("ex6", 0), ("spd65", 3), ("spd257", 0), ("one", 1)])
 def test_fields_against_longdouble(name, k, C_):
     """three updates; the reference and the bounds of rbstats_cases.fields_reference.

@@ -32,6 +32,8 @@ def test_case_table_covers_the_lane_splits():
     assert {lpr_log2_of(C) for C in R.CHAINS} == set(range(7))
     assert 64 in R.CHAINS and 65 in R.CHAINS and any(C > 64 and C % 64 not in (0, 1) for C in R.CHAINS)  # chunk boundary, partial last chunk
     assert any((1 << lpr_log2_of(C)) != C and C < 64 for C in R.CHAINS)  # a partial lane group
+    assert R.MORE_CHAINS == [4, 16, 32, 63, 128, 129] and not set(R.MORE_CHAINS) & set(R.CHAINS)
+    assert [lpr_log2_of(C) for C in R.MORE_CHAINS] == [2, 4, 5, 6, 6, 6]  # full lane groups; one dead lane; 2 and 3 chunks
     assert R.RANKS[:3] == [0, 1, 3] and R.RANKS[3] > 3
     for n in (65, 257):
         B, S = R.lowrank(n, 3, seed=n)
@@ -71,7 +73,7 @@ def test_diagonal_matrix_gives_b_over_q(dyadic):
     assert np.array_equal(m, np.broadcast_to((b.astype(np.longdouble) / q.astype(np.longdouble))[:, None], m.shape))
     if dyadic:  # exact in float64, and C b / q is exact for every C of the table: the device mean is b / q bit for bit
         assert np.array_equal(m.astype(np.float64).astype(np.longdouble), m)
-        for C_ in R.CHAINS:
+        for C_ in R.CHAINS + R.MORE_CHAINS:
             assert np.array_equal((C_ * (b / q)) / C_, b / q)
 
 
