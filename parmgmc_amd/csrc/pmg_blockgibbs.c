@@ -268,7 +268,7 @@ static pmg_status bg_chains_run(pmg_blockgibbs bg, int32_t C, const uint64_t *se
   const int      ndir = pmg_sweep_ndir(bg->type);
   pmg_sweep_iter it   = pmg_sweep_begin(bg->type, its, noisy, counter0);
   while (pmg_sweep_next(&it)) {
-    PMG_CALL(pmg_blockgibbs_dir_sweep_chains(bg, it.dir, noisy, C, noisy ? bg->ch_keys.dev : NULL, it.sweep, NULL, b, bcs, Y, stream));
+    PMG_CALL(pmg_blockgibbs_dir_sweep_chains(bg, it.dir, noisy, C, noisy ? bg->ch_keys.dev.p : NULL, it.sweep, NULL, b, bcs, Y, stream));
     if (cb && (it.index + 1) % ndir == 0) { /* a sample is complete */
       const int rc = cb((int32_t)(it.index / ndir), Y, (int32_t)bg_len(bg), C, cbctx);
       PMG_CHECK(rc == 0, rc, "sample callback returned %d", rc);

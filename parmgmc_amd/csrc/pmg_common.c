@@ -53,6 +53,30 @@ void pmg_dev_free(void *p)
   if (p) (void)hipFree(p);
 }
 
+/* The growth rule of every workspace that follows the chain count (include/parmgmc_hip.h: a call that has to allocate or grow
+   synchronises `stream` and returns when the new buffer is zero-filled; with the sizes of an earlier call nothing synchronises;
+   a failing call leaves the object usable).  Enough capacity: no HIP call.  Otherwise the stream is synchronised, because
+   launches enqueued by earlier calls may still use the old buffer, which hipFree would take from under them.  cap is zero while
+   there is no buffer, so after a failed allocation the next call allocates afresh. */
+pmg_status pmg_devbuf_reserve(pmg_devbuf *b, size_t bytes, void *stream)
+{
+  if (bytes == 0) bytes = 8; /* as pmg_dev_alloc: p is never NULL after a reserve */
+  if (bytes <= b->cap) return PMG_SUCCESS;
+  PMG_HIP(hipStreamSynchronize((hipStream_t)stream));
+  pmg_devbuf_free(b);
+  const pmg_status st = pmg_dev_alloc(&b->p, bytes);
+  if (st) pmg_devbuf_free(b); /* the zero fill failed */
+  else b->cap = bytes;
+  return st;
+}
+
+void pmg_devbuf_free(pmg_devbuf *b)
+{
+  pmg_dev_free(b->p);
+  b->p   = NULL;
+  b->cap = 0;
+}
+
 pmg_status pmg_vec_set_random_standard_normal(int64_t n, double *x_dev, uint64_t seed, uint64_t counter, void *stream)
 {
   PMG_CHECK(n >= 0, PMG_ERR_ARG_OUTOFRANGE, "negative length %lld", (long long)n);

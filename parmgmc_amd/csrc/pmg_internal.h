@@ -146,12 +146,20 @@ pmg_status pmg_dev_alloc(void **p, size_t bytes); /* zero-filled; the fill has f
 pmg_status pmg_dev_zero(void *p, size_t bytes);   /* zero fill, finished on return */
 pmg_status pmg_dev_upload(void **p, const void *host, size_t bytes);
 void       pmg_dev_free(void *p);
-
-
-/* multi-chain entry points (pmg_mcsor.c): a device copy of C noise keys, uploaded only when they change */
+/* a device buffer that grows: the workspaces whose size follows the chain count.  Zero-filled whenever (re)allocated; reserve
+   with bytes <= cap makes no HIP call, a growing one synchronises `stream` first; a failed one leaves {NULL, 0} */
 typedef struct {
-  uint64_t *dev, *host;
-  int64_t   cap, n;
+  void  *p;
+  size_t cap; /* bytes */
+} pmg_devbuf;
+pmg_status pmg_devbuf_reserve(pmg_devbuf *b, size_t bytes, void *stream);
+void       pmg_devbuf_free(pmg_devbuf *b);
+
+/* shared by every multi-chain entry point (pmg_chains_common.c): a device copy of C noise keys, uploaded only when they change */
+typedef struct {
+  pmg_devbuf dev;
+  uint64_t  *host; /* the keys of the last upload; as long as dev */
+  int64_t    n;
 } pmg_keybuf;
 pmg_status pmg_keybuf_set(pmg_keybuf *k, const uint64_t *keys, int64_t n, void *stream);
 void       pmg_keybuf_free(pmg_keybuf *k);

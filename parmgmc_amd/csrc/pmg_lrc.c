@@ -53,13 +53,12 @@ struct pmg_lrc_s {
   int      empty;            /* this rank's rows do not meet the support of B at all (row-distributed operator) */
   pmg_lrc_reduce_fn reduce;  /* row-distributed operator: sum of the k-vectors over the ranks */
   void             *rctx;
-  /* many chains (pmg_lrc_rhs_chains / pmg_lrc_post_chains): k x ch_cap k-vectors and the block sums of B^T Y, first use */
-  int32_t ch_cap;
-  double *ch_eta, *ch_wk, *ch_partial;
-  /* the chains V-cycle (pmg_lrc_rhs_inplace_chains): the right-hand side entries under the noise term, (ns or ld) x ch_saved_cap,
+  /* many chains (pmg_lrc_rhs_chains / pmg_lrc_post_chains): k x C k-vectors and the block sums of B^T Y, first use */
+  pmg_devbuf ch_eta, ch_wk, ch_partial;
+  /* the chains V-cycle (pmg_lrc_rhs_inplace_chains): the right-hand side entries under the noise term, (ns or ld) x C,
      and the vector that carries it until the next repair puts them back */
-  int32_t ch_saved_cap;
-  double *ch_saved, *ch_bmod;
+  pmg_devbuf ch_saved;
+  double    *ch_bmod;
 };
 
 void pmg_lrc_destroy(pmg_lrc *p)
@@ -82,10 +81,10 @@ void pmg_lrc_destroy(pmg_lrc *p)
   pmg_dev_free(l->Bbc[0]);
   pmg_dev_free(l->Bbc[1]);
   pmg_dev_free(l->saved);
-  pmg_dev_free(l->ch_eta);
-  pmg_dev_free(l->ch_wk);
-  pmg_dev_free(l->ch_partial);
-  pmg_dev_free(l->ch_saved);
+  pmg_devbuf_free(&l->ch_eta);
+  pmg_devbuf_free(&l->ch_wk);
+  pmg_devbuf_free(&l->ch_partial);
+  pmg_devbuf_free(&l->ch_saved);
   free(l);
   *p = NULL;
 }
@@ -512,20 +511,10 @@ pmg_status pmg_lrc_dir_sweep(pmg_lrc l, int noisy, int dir, uint64_t seed, uint6
 static pmg_status lrc_chains_workspace(pmg_lrc l, int32_t C, void *stream)
 {
   PMG_CHECK(pmg_lrc_is_local(l), PMG_ERR_SUP, "the chain forms of the low-rank update need an update on one device");
-  if (C <= l->ch_cap) return PMG_SUCCESS;
-  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffers may still be in use */
-  pmg_dev_free(l->ch_eta);
-  pmg_dev_free(l->ch_wk);
-  pmg_dev_free(l->ch_partial);
-  l->ch_eta = l->ch_wk = l->ch_partial = NULL;
-  l->ch_cap                            = 0;
-  const size_t kc = (size_t)l->k * (size_t)C;
-  const int    nb = pmgk_lrc_btx_chains_nblocks(l->ns ? l->ns : l->ld, l->ns > 0);
-  PMG_CALL(pmg_dev_alloc((void **)&l->ch_eta, sizeof(double) * kc));
-  PMG_CALL(pmg_dev_alloc((void **)&l->ch_wk, sizeof(double) * kc));
-  PMG_CALL(pmg_dev_alloc((void **)&l->ch_partial, sizeof(double) * kc * (size_t)nb));
-  l->ch_cap = C;
-  return PMG_SUCCESS;
+  const size_t kc = sizeof(double) * (size_t)l->k * (size_t)C;
+  PMG_CALL(pmg_devbuf_reserve(&l->ch_eta, kc, stream));
+  PMG_CALL(pmg_devbuf_reserve(&l->ch_wk, kc, stream));
+  return pmg_devbuf_reserve(&l->ch_partial, kc * (size_t)pmgk_lrc_btx_chains_nblocks(l->ns ? l->ns : l->ld, l->ns > 0), stream);
 }
 
 /* the right-hand sides of a noisy sweep on C chains: out = b + B (sqrt(S) o eta_c) on the support rows (every row in the dense
@@ -535,9 +524,9 @@ pmg_status pmg_lrc_rhs_chains(pmg_lrc l, int32_t C, const uint64_t *keys_dev, ui
 {
   PMG_CALL(lrc_chains_workspace(l, C, stream));
   PMG_CALL(lrc_flush_restore(l, stream));
-  PMG_KERNEL(pmgk_lrc_noise_chains(l->k, C, keys_dev, pmg_lrc_noise_seed(0), counter, l->sqrtS, l->ch_eta, stream));
-  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bc, l->ns, l->ch_eta, 1.0, b_lay, b_cs, out_lay, C, stream));
-  else PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->B, l->ld, l->ch_eta, 1.0, b_lay, b_cs, out_lay, C, stream));
+  PMG_KERNEL(pmgk_lrc_noise_chains(l->k, C, keys_dev, pmg_lrc_noise_seed(0), counter, l->sqrtS, l->ch_eta.p, stream));
+  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bc, l->ns, l->ch_eta.p, 1.0, b_lay, b_cs, out_lay, C, stream));
+  else PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->B, l->ld, l->ch_eta.p, 1.0, b_lay, b_cs, out_lay, C, stream));
   return PMG_SUCCESS;
 }
 
@@ -549,11 +538,11 @@ pmg_status pmg_lrc_post_chains(pmg_lrc l, int32_t C, int dir, double *Y_lay, voi
   PMG_CALL(lrc_flush_restore(l, stream));
   l->bty_vec = NULL;
   if (l->ns) {
-    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, Y_lay, C, l->ch_partial, NULL, l->ch_wk, stream));
-    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bbc[d], l->ns, l->ch_wk, -1.0, Y_lay, 1, Y_lay, C, stream));
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, Y_lay, C, l->ch_partial.p, NULL, l->ch_wk.p, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ns, l->rows, l->k, l->Bbc[d], l->ns, l->ch_wk.p, -1.0, Y_lay, 1, Y_lay, C, stream));
   } else {
-    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, Y_lay, C, l->ch_partial, NULL, l->ch_wk, stream));
-    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->Bb[d], l->ld, l->ch_wk, -1.0, Y_lay, 1, Y_lay, C, stream));
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, Y_lay, C, l->ch_partial.p, NULL, l->ch_wk.p, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_chains(l->ld, NULL, l->k, l->Bb[d], l->ld, l->ch_wk.p, -1.0, Y_lay, 1, Y_lay, C, stream));
   }
   return PMG_SUCCESS;
 }
@@ -572,18 +561,11 @@ int pmg_lrc_chains_fused(pmg_lrc l) { return l && lrc_small_chains(l); }
 pmg_status pmg_lrc_rhs_inplace_chains(pmg_lrc l, int32_t C, const double *eta_dev, double *B_lay, void *stream)
 {
   PMG_CALL(lrc_chains_workspace(l, C, stream));
-  if (C > l->ch_saved_cap) {
-    PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
-    pmg_dev_free(l->ch_saved);
-    l->ch_saved     = NULL;
-    l->ch_saved_cap = 0;
-    PMG_CALL(pmg_dev_alloc((void **)&l->ch_saved, sizeof(double) * (size_t)(l->ns ? l->ns : l->ld) * (size_t)C));
-    l->ch_saved_cap = C;
-  }
+  PMG_CALL(pmg_devbuf_reserve(&l->ch_saved, sizeof(double) * (size_t)(l->ns ? l->ns : l->ld) * (size_t)C, stream));
   PMG_CALL(lrc_flush_restore(l, stream)); /* a single-chain call's, should one be pending */
   l->ch_bmod = NULL; /* (a cycle that ended in an error: its right-hand sides are rewritten before they are read again) */
-  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, l->Bc, l->ns, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved, NULL, NULL, stream));
-  else PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, l->B, l->ld, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved, NULL, NULL, stream));
+  if (l->ns) PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, l->Bc, l->ns, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved.p, NULL, NULL, stream));
+  else PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, l->B, l->ld, eta_dev, 1.0, B_lay, 1, B_lay, C, l->ch_saved.p, NULL, NULL, stream));
   l->ch_bmod = B_lay;
   return PMG_SUCCESS;
 }
@@ -591,15 +573,15 @@ pmg_status pmg_lrc_rhs_inplace_chains(pmg_lrc l, int32_t C, const double *eta_de
 /* out -= M2 (scale o (B^T X)) on C chains; restore: the entries pmg_lrc_rhs_inplace_chains kept go back in the update's pass */
 static pmg_status lrc_btx_update_chains(pmg_lrc l, int32_t C, const double *X_lay, const double *scale, const double *M2c, const double *M2d, double *out_lay, int restore, void *stream)
 {
-  const double *sv = restore ? l->ch_saved : NULL;
+  const double *sv = restore ? l->ch_saved.p : NULL;
   double       *bm = restore ? l->ch_bmod : NULL;
   if (lrc_small_chains(l)) PMG_KERNEL(pmgk_lrc_small_chains(l->ns, l->rows, l->k, l->Bc, X_lay, C, scale, M2c, -1.0, out_lay, sv, bm, stream));
   else if (l->ns) {
-    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, X_lay, C, l->ch_partial, scale, l->ch_wk, stream));
-    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, M2c, l->ns, l->ch_wk, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ns, l->rows, l->k, l->Bc, l->ns, X_lay, C, l->ch_partial.p, scale, l->ch_wk.p, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ns, l->rows, l->k, M2c, l->ns, l->ch_wk.p, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
   } else {
-    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, X_lay, C, l->ch_partial, scale, l->ch_wk, stream));
-    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, M2d, l->ld, l->ch_wk, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
+    PMG_KERNEL(pmgk_lrc_btx_chains(l->ld, NULL, l->k, l->B, l->ld, X_lay, C, l->ch_partial.p, scale, l->ch_wk.p, stream));
+    PMG_KERNEL(pmgk_lrc_axpy_save_chains(l->ld, NULL, l->k, M2d, l->ld, l->ch_wk.p, -1.0, out_lay, 1, out_lay, C, NULL, sv, bm, stream));
   }
   return PMG_SUCCESS;
 }

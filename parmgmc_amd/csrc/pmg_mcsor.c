@@ -38,13 +38,11 @@ struct pmg_mcsor_s {
   pmg_lrc  lrc;             /* MATLRC: rank-k update B S B^T (src/mc_sor.c:572-595) */
   int64_t  noise_row0;      /* global row of local row 0 (row block of a distributed matrix) */
   /* multi-chain workspace (pmg_mcsor_*_chains): allocated on first use, grows with the chain count */
-  int32_t    ch_cap;  /* chains ch_Y holds */
-  double    *ch_b;    /* [ld] the shared right-hand side in the layout */
-  double    *ch_Y;    /* [ld * ch_cap] the chains in the layout, chain fastest */
+  pmg_devbuf ch_b;    /* [ld] the shared right-hand side in the layout */
+  pmg_devbuf ch_Y;    /* [ld * C] the chains in the layout, chain fastest */
   pmg_keybuf ch_keys; /* the chains' noise keys */
-  int32_t    ch_B_cap, ch_bc_cap;
-  double    *ch_B;  /* [ld * ch_B_cap] one right-hand side per chain in the layout (pmg_mcsor_sample_chains_rhs) */
-  double    *ch_bc; /* [ld * ch_bc_cap] the right-hand sides of a noisy sweep with the low-rank noise term */
+  pmg_devbuf ch_B;    /* [ld * C] one right-hand side per chain in the layout (pmg_mcsor_sample_chains_rhs) */
+  pmg_devbuf ch_bc;   /* [ld * C] the right-hand sides of a noisy sweep with the low-rank noise term */
 };
 
 /* --- colouring rules -------------------------------------------------------------------------------- */
@@ -265,20 +263,13 @@ pmg_status pmg_mcsor_set_coloring(pmg_mcsor mc, int rule, const int32_t *user_co
   return PMG_SUCCESS;
 }
 
-static void mcsor_free_chains(pmg_mcsor mc)
-{
-  pmg_dev_free(mc->ch_b);
-  pmg_dev_free(mc->ch_Y);
-  pmg_dev_free(mc->ch_B);
-  pmg_dev_free(mc->ch_bc);
-  pmg_keybuf_free(&mc->ch_keys);
-  mc->ch_b = mc->ch_Y = mc->ch_B = mc->ch_bc = NULL;
-  mc->ch_cap = mc->ch_B_cap = mc->ch_bc_cap = 0;
-}
-
 static void mcsor_free_setup(pmg_mcsor mc)
 {
-  mcsor_free_chains(mc);
+  pmg_devbuf_free(&mc->ch_b);
+  pmg_devbuf_free(&mc->ch_Y);
+  pmg_devbuf_free(&mc->ch_B);
+  pmg_devbuf_free(&mc->ch_bc);
+  pmg_keybuf_free(&mc->ch_keys);
   free(mc->colors);
   free(mc->cslice);
   free(mc->orig_host);
@@ -722,40 +713,6 @@ pmg_status pmg_mcsor_set_lowrank(pmg_mcsor mc, int32_t k, const double *B_host, 
    The iterate of C chains lives in the layout as ld x C doubles, chain fastest; one launch per colour sweeps every chain
    (kernels_chains.hip).  Column c follows exactly the single-chain path: same colour order, same counters, key seeds[c]. */
 
-pmg_status pmg_keybuf_set(pmg_keybuf *k, const uint64_t *keys, int64_t n, void *stream)
-{
-  if (k->n == n && n > 0 && !memcmp(k->host, keys, sizeof(uint64_t) * (size_t)n)) return PMG_SUCCESS;
-  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* launches in flight may still read the keys; the host copy is the source of the last upload */
-  if (n > k->cap) {
-    pmg_keybuf_free(k);
-    k->host = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)n);
-    PMG_CHECK(k->host, PMG_ERR_MEM, "out of host memory");
-    PMG_CALL(pmg_dev_alloc((void **)&k->dev, sizeof(uint64_t) * (size_t)n));
-    k->cap = n;
-  }
-  memcpy(k->host, keys, sizeof(uint64_t) * (size_t)n);
-  k->n = n;
-  PMG_HIP(hipMemcpyAsync(k->dev, k->host, sizeof(uint64_t) * (size_t)n, hipMemcpyHostToDevice, (hipStream_t)stream));
-  return PMG_SUCCESS;
-}
-
-void pmg_keybuf_free(pmg_keybuf *k)
-{
-  pmg_dev_free(k->dev);
-  free(k->host);
-  memset(k, 0, sizeof *k);
-}
-
-/* the launches index ld x C elements with 64-bit offsets; grids of 256-thread blocks over them and chunks of 64 chains in
-   blockIdx.y must stay inside the launch limits */
-pmg_status pmg_chains_size_check(int64_t ld, int32_t nchains)
-{
-  PMG_CHECK(nchains >= 1, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d", nchains);
-  PMG_CHECK(nchains <= 64 * 65535, PMG_ERR_ARG_OUTOFRANGE, "nchains = %d exceeds %d", nchains, 64 * 65535);
-  PMG_CHECK(ld <= ((int64_t)1 << 40) / nchains, PMG_ERR_ARG_OUTOFRANGE, "%lld rows x %d chains exceed 2^40 elements", (long long)ld, nchains);
-  return PMG_SUCCESS;
-}
-
 /* what the V-cycle of the chains carries (pmg_mgmc_sample_chains): a low-rank update on one device */
 pmg_status pmg_mcsor_chains_supported(pmg_mcsor mc)
 {
@@ -836,20 +793,6 @@ pmg_status pmg_mcsor_residual_chains(pmg_mcsor mc, int32_t nchains, const double
   return PMG_SUCCESS;
 }
 
-static pmg_status mcsor_chains_workspace(pmg_mcsor mc, int32_t nchains, void *stream)
-{
-  if (!mc->ch_b) PMG_CALL(pmg_dev_alloc((void **)&mc->ch_b, sizeof(double) * (size_t)mc->S.ld));
-  if (nchains > mc->ch_cap) {
-    PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
-    pmg_dev_free(mc->ch_Y);
-    mc->ch_Y   = NULL;
-    mc->ch_cap = 0;
-    PMG_CALL(pmg_dev_alloc((void **)&mc->ch_Y, sizeof(double) * (size_t)mc->S.ld * (size_t)nchains));
-    mc->ch_cap = nchains;
-  }
-  return PMG_SUCCESS;
-}
-
 /* argument checks of both entry points, before any device work */
 static pmg_status mcsor_chains_args(pmg_mcsor mc, int32_t nchains, int need_seeds, const uint64_t *seeds, const double *b, const double *Y)
 {
@@ -860,39 +803,25 @@ static pmg_status mcsor_chains_args(pmg_mcsor mc, int32_t nchains, int need_seed
   return pmg_chains_size_check(mc->S.ld, nchains);
 }
 
-/* ld x C layout buffer of its own capacity */
-static pmg_status mcsor_chains_buf(pmg_mcsor mc, double **buf, int32_t *cap, int32_t nchains, void *stream)
-{
-  if (nchains <= *cap) return PMG_SUCCESS;
-  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
-  pmg_dev_free(*buf);
-  *buf = NULL;
-  *cap = 0;
-  PMG_CALL(pmg_dev_alloc((void **)buf, sizeof(double) * (size_t)mc->S.ld * (size_t)nchains));
-  *cap = nchains;
-  return PMG_SUCCESS;
-}
-
 /* the chains entry points: right-hand side b_nat shared (bcs = 0, n values) or one per chain (bcs = 1, n x C, chain fastest) */
 static pmg_status mcsor_chains_run(pmg_mcsor mc, int32_t nchains, const uint64_t *seeds, int noisy, const double *b_nat, int bcs, double *Y, int32_t its, int scaled, uint64_t counter0, uint64_t *counter_out, void *stream)
 {
   PMG_CALL(mcsor_ready(mc));
-  PMG_CALL(mcsor_chains_workspace(mc, nchains, stream));
+  const int    term = mc->lrc && noisy; /* the noisy sweeps' right-hand sides: b everywhere, the support rows rewritten before every sweep */
+  const size_t vec  = sizeof(double) * (size_t)mc->S.ld;
+  PMG_CALL(pmg_devbuf_reserve(&mc->ch_b, vec, stream));
+  PMG_CALL(pmg_devbuf_reserve(&mc->ch_Y, vec * (size_t)nchains, stream));
+  if (bcs) PMG_CALL(pmg_devbuf_reserve(&mc->ch_B, vec * (size_t)nchains, stream));
+  if (term) PMG_CALL(pmg_devbuf_reserve(&mc->ch_bc, vec * (size_t)nchains, stream));
   if (noisy) PMG_CALL(pmg_keybuf_set(&mc->ch_keys, seeds, nchains, stream));
-  const double *b_lay = mc->ch_b;
-  if (bcs) {
-    PMG_CALL(mcsor_chains_buf(mc, &mc->ch_B, &mc->ch_B_cap, nchains, stream));
-    PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, 1, mc->ch_B, stream));
-    b_lay = mc->ch_B;
-  } else PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b_nat, mc->ch_b, stream));
-  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y, stream));
-  const uint64_t *keys = noisy ? mc->ch_keys.dev : NULL;
-  if (mc->lrc && noisy) { /* the noisy sweeps' right-hand sides: b everywhere, the support rows rewritten before every sweep */
-    PMG_CALL(mcsor_chains_buf(mc, &mc->ch_bc, &mc->ch_bc_cap, nchains, stream));
-    PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, bcs, mc->ch_bc, stream));
-  }
-  PMG_CALL(mcsor_sweeps_chains(mc, mc->lrc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_bc, mc->ch_Y, stream));
-  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y, Y, stream));
+  const double *b_lay = bcs ? mc->ch_B.p : mc->ch_b.p;
+  if (bcs) PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, 1, mc->ch_B.p, stream));
+  else PMG_KERNEL(pmgk_permute_in(mc->S.ld, mc->S.orig, b_nat, mc->ch_b.p, stream));
+  PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, Y, 1, mc->ch_Y.p, stream));
+  const uint64_t *keys = noisy ? mc->ch_keys.dev.p : NULL;
+  if (term) PMG_KERNEL(pmgk_permute_in_chains(mc->S.ld, mc->S.orig, nchains, b_nat, bcs, mc->ch_bc.p, stream));
+  PMG_CALL(mcsor_sweeps_chains(mc, mc->lrc, nchains, keys, noisy, scaled, its, counter0, counter_out, b_lay, bcs, mc->ch_bc.p, mc->ch_Y.p, stream));
+  PMG_KERNEL(pmgk_permute_out_chains(mc->S.ld, mc->S.orig, nchains, mc->ch_Y.p, Y, stream));
   return PMG_SUCCESS;
 }
 

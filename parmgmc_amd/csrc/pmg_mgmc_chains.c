@@ -15,54 +15,39 @@ static pmg_lrc chains_lrc(const struct pmg_mgmc_s *h, int l) { return h->lv[l].m
 
 void pmg_mgmc_i_free_chains(pmg_mgmc h)
 {
-  for (int l = 0; l < h->nlevels && h->ch_b; ++l) {
-    pmg_dev_free(h->ch_b[l]);
-    pmg_dev_free(h->ch_x[l]);
-    pmg_dev_free(h->ch_r[l]);
-  }
+  for (int l = 0; l < 3 * h->nlevels && h->ch_b; ++l) pmg_devbuf_free(&h->ch_b[l]); /* ch_b, ch_x, ch_r: one array (mgmc_chains_workspace) */
   free(h->ch_b);
-  free(h->ch_x);
-  free(h->ch_r);
-  pmg_dev_free(h->ch_Y);
-  pmg_dev_free(h->ch_bs);
-  pmg_dev_free(h->ch_xi);
-  pmg_dev_free(h->ch_v);
-  pmg_dev_free(h->ch_B);
-  pmg_dev_free(h->ch_eta);
-  pmg_keybuf_free(&h->ch_keys);
   h->ch_b = h->ch_x = h->ch_r = NULL;
-  h->ch_Y = h->ch_bs = h->ch_xi = h->ch_v = h->ch_B = h->ch_eta = NULL;
-  h->ch_cap = h->ch_B_cap = 0;
-  h->ch_eta_cap = 0;
+  pmg_devbuf_free(&h->ch_Y);
+  pmg_devbuf_free(&h->ch_bs);
+  pmg_devbuf_free(&h->ch_xi);
+  pmg_devbuf_free(&h->ch_v);
+  pmg_devbuf_free(&h->ch_B);
+  pmg_devbuf_free(&h->ch_eta);
+  pmg_keybuf_free(&h->ch_keys);
 }
 
 static pmg_status mgmc_chains_workspace(pmg_mgmc h, int32_t C, void *stream)
 {
-  if (C <= h->ch_cap) return PMG_SUCCESS;
-  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffers may still be in use */
-  pmg_keybuf keys = h->ch_keys; /* kept: its own growth rule */
-  memset(&h->ch_keys, 0, sizeof h->ch_keys);
-  pmg_mgmc_i_free_chains(h);
-  h->ch_keys = keys;
-  const int L = h->nlevels;
-  h->ch_b = (double **)calloc((size_t)L, sizeof(double *));
-  h->ch_x = (double **)calloc((size_t)L, sizeof(double *));
-  h->ch_r = (double **)calloc((size_t)L, sizeof(double *));
-  PMG_CHECK(h->ch_b && h->ch_x && h->ch_r, PMG_ERR_MEM, "out of host memory");
-  for (int l = 0; l < L; ++l) {
+  if (!h->ch_b) { /* first chains call: the three level arrays, empty, in one host allocation */
+    h->ch_b = (pmg_devbuf *)calloc(3 * (size_t)h->nlevels, sizeof(pmg_devbuf));
+    PMG_CHECK(h->ch_b, PMG_ERR_MEM, "out of host memory");
+    h->ch_x = h->ch_b + h->nlevels;
+    h->ch_r = h->ch_x + h->nlevels;
+  }
+  for (int l = 0; l < h->nlevels; ++l) {
     const size_t bytes = sizeof(double) * (size_t)h->lv[l].ld * (size_t)C;
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_b[l], bytes));
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_x[l], bytes));
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_r[l], bytes));
+    PMG_CALL(pmg_devbuf_reserve(&h->ch_b[l], bytes, stream));
+    PMG_CALL(pmg_devbuf_reserve(&h->ch_x[l], bytes, stream));
+    PMG_CALL(pmg_devbuf_reserve(&h->ch_r[l], bytes, stream));
   }
-  const mg_level *F = &h->lv[L - 1];
-  PMG_CALL(pmg_dev_alloc((void **)&h->ch_Y, sizeof(double) * (size_t)F->ld * (size_t)C));
-  PMG_CALL(pmg_dev_alloc((void **)&h->ch_bs, sizeof(double) * (size_t)F->ld));
+  const size_t top = sizeof(double) * (size_t)h->lv[h->nlevels - 1].ld;
+  PMG_CALL(pmg_devbuf_reserve(&h->ch_Y, top * (size_t)C, stream));
+  PMG_CALL(pmg_devbuf_reserve(&h->ch_bs, top, stream));
   if (h->coarse_type == 0) {
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_xi, sizeof(double) * (size_t)h->lv[0].n * (size_t)C));
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_v, sizeof(double) * (size_t)h->lv[0].n * (size_t)C));
+    PMG_CALL(pmg_devbuf_reserve(&h->ch_xi, sizeof(double) * (size_t)h->lv[0].n * (size_t)C, stream));
+    PMG_CALL(pmg_devbuf_reserve(&h->ch_v, sizeof(double) * (size_t)h->lv[0].n * (size_t)C, stream));
   }
-  h->ch_cap = C;
   return PMG_SUCCESS;
 }
 
@@ -87,17 +72,9 @@ static pmg_status chains_draw_lowrank_noise(pmg_mgmc h, int32_t C, const uint64_
     any = lr;
   }
   if (!nslots) return PMG_SUCCESS;
-  const int     k    = pmg_lrc_rank(any);
-  const int64_t need = (int64_t)nslots * k * C;
-  if (need > h->ch_eta_cap) {
-    PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffer may still be in use */
-    pmg_dev_free(h->ch_eta);
-    h->ch_eta     = NULL;
-    h->ch_eta_cap = 0;
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_eta, sizeof(double) * (size_t)need));
-    h->ch_eta_cap = need;
-  }
-  PMG_KERNEL(pmgk_lrc_noise_batch_chains(nslots, k, C, keys, pmg_lrc_noise_seed(0), &plan, pmg_lrc_sqrtS(any), h->ch_eta, stream)); /* S is the same on every level (src/pc_gamgmc.c:170-176) */
+  const int k = pmg_lrc_rank(any);
+  PMG_CALL(pmg_devbuf_reserve(&h->ch_eta, sizeof(double) * (size_t)nslots * (size_t)k * (size_t)C, stream));
+  PMG_KERNEL(pmgk_lrc_noise_batch_chains(nslots, k, C, keys, pmg_lrc_noise_seed(0), &plan, pmg_lrc_sqrtS(any), h->ch_eta.p, stream)); /* S is the same on every level (src/pc_gamgmc.c:170-176) */
   return PMG_SUCCESS;
 }
 
@@ -109,7 +86,7 @@ static pmg_status chains_smooth(pmg_mgmc h, int l, int32_t C, const uint64_t *ke
   pmg_lrc   lr = chains_lrc(h, l);
   if (!lr) return pmg_mcsor_sweeps_chains(Lv->mc, C, keys + (size_t)l * C, 1, h->scaled, its, *ctr, ctr, b, bcs, x, stream);
   const int64_t kc = (int64_t)pmg_lrc_rank(lr) * C;
-  PMG_CALL(pmg_mcsor_sweeps_lowrank_chains(Lv->mc, C, keys + (size_t)l * C, h->scaled, its, *ctr, ctr, h->ch_eta + (int64_t)(first + *done) * kc, kc, bown, x, stream));
+  PMG_CALL(pmg_mcsor_sweeps_lowrank_chains(Lv->mc, C, keys + (size_t)l * C, h->scaled, its, *ctr, ctr, (const double *)h->ch_eta.p + (int64_t)(first + *done) * kc, kc, bown, x, stream));
   *done += pmg_mgmc_i_leg_sweeps(h, l);
   return PMG_SUCCESS;
 }
@@ -130,29 +107,29 @@ static pmg_status mg_vcycle_chains(pmg_mgmc h, int32_t C, const uint64_t *keys, 
   if (h->lrc_k > 0) PMG_CALL(chains_draw_lowrank_noise(h, C, keys, ctr, first, stream));
   for (int l = top; l >= 1; --l) {
     mg_level     *Lv  = &h->lv[l];
-    const double *b   = l == top ? btop : h->ch_b[l];
+    const double *b   = l == top ? btop : h->ch_b[l].p;
     const int     bcs = l == top ? bcs_top : 1;
-    double       *x   = l == top ? xtop : h->ch_x[l];
+    double       *x   = l == top ? xtop : h->ch_x[l].p;
     if ((l < top || !top_has_guess) && !zeroed[l]) PMG_KERNEL(pmgk_fill_zero(x, Lv->ld * C, stream));
-    PMG_CALL(chains_smooth(h, l, C, keys, h->nu, &ctr[l], first[l], &done[l], b, bcs, l == top ? btop_own : h->ch_b[l], x, stream));
-    PMG_CALL(pmg_mcsor_residual_chains(Lv->mc, C, b, bcs, x, h->ch_r[l], stream)); /* with the low-rank term of a MATLRC level, src/pc_gamgmc.c:194 */
+    PMG_CALL(chains_smooth(h, l, C, keys, h->nu, &ctr[l], first[l], &done[l], b, bcs, l == top ? btop_own : h->ch_b[l].p, x, stream));
+    PMG_CALL(pmg_mcsor_residual_chains(Lv->mc, C, b, bcs, x, h->ch_r[l].p, stream)); /* with the low-rank term of a MATLRC level, src/pc_gamgmc.c:194 */
     /* b_{l-1} = P^T r, which also sets the coarse level's zero guess where one is needed (as mg_restrict does) */
     const int needs_zero = l - 1 >= 1 || h->coarse_type != 0;
-    PMG_KERNEL(pmgk_csr_spmv_rows_chains(Lv->R_nrows, Lv->R_rowpos, Lv->R_rowptr, Lv->R_col, Lv->R_val, C, h->ch_r[l], h->ch_b[l - 1], 0, needs_zero ? h->ch_x[l - 1] : NULL, stream));
+    PMG_KERNEL(pmgk_csr_spmv_rows_chains(Lv->R_nrows, Lv->R_rowpos, Lv->R_rowptr, Lv->R_col, Lv->R_val, C, h->ch_r[l].p, h->ch_b[l - 1].p, 0, needs_zero ? h->ch_x[l - 1].p : NULL, stream));
     zeroed[l - 1] = needs_zero;
   }
-  if (h->coarse_type == 0) PMG_CALL(pmg_chol_sample_chains(h->chol, C, keys, ctr[0], h->ch_b[0], h->ch_x[0], h->ch_xi, h->ch_v, stream));
+  if (h->coarse_type == 0) PMG_CALL(pmg_chol_sample_chains(h->chol, C, keys, ctr[0], h->ch_b[0].p, h->ch_x[0].p, h->ch_xi.p, h->ch_v.p, stream));
   else {
-    if (!zeroed[0]) PMG_KERNEL(pmgk_fill_zero(h->ch_x[0], h->lv[0].ld * C, stream));
-    PMG_CALL(chains_smooth(h, 0, C, keys, h->coarse_its, &ctr[0], first[0], &done[0], h->ch_b[0], 1, h->ch_b[0], h->ch_x[0], stream));
+    if (!zeroed[0]) PMG_KERNEL(pmgk_fill_zero(h->ch_x[0].p, h->lv[0].ld * C, stream));
+    PMG_CALL(chains_smooth(h, 0, C, keys, h->coarse_its, &ctr[0], first[0], &done[0], h->ch_b[0].p, 1, h->ch_b[0].p, h->ch_x[0].p, stream));
   }
   for (int l = 1; l <= top; ++l) {
     mg_level     *Lv  = &h->lv[l];
-    const double *b   = l == top ? btop : h->ch_b[l];
+    const double *b   = l == top ? btop : h->ch_b[l].p;
     const int     bcs = l == top ? bcs_top : 1;
-    double       *x   = l == top ? xtop : h->ch_x[l];
-    PMG_KERNEL(pmgk_csr_spmv_rows_chains(Lv->P_nrows, Lv->P_rowpos, Lv->P_rowptr, Lv->P_col, Lv->P_val, C, h->ch_x[l - 1], x, 1, NULL, stream)); /* x += P e */
-    PMG_CALL(chains_smooth(h, l, C, keys, h->nu, &ctr[l], first[l], &done[l], b, bcs, l == top ? btop_own : h->ch_b[l], x, stream));
+    double       *x   = l == top ? xtop : h->ch_x[l].p;
+    PMG_KERNEL(pmgk_csr_spmv_rows_chains(Lv->P_nrows, Lv->P_rowpos, Lv->P_rowptr, Lv->P_col, Lv->P_val, C, h->ch_x[l - 1].p, x, 1, NULL, stream)); /* x += P e */
+    PMG_CALL(chains_smooth(h, l, C, keys, h->nu, &ctr[l], first[l], &done[l], b, bcs, l == top ? btop_own : h->ch_b[l].p, x, stream));
   }
   return PMG_SUCCESS;
 }
@@ -186,14 +163,7 @@ static pmg_status mgmc_chains_run(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   const int top = h->nlevels - 1;
   mg_level *F   = &h->lv[top];
   PMG_CALL(mgmc_chains_workspace(h, C, stream));
-  if (bcs && C > h->ch_B_cap) { /* after the workspace: growing it frees this buffer too */
-    PMG_HIP(hipStreamSynchronize((hipStream_t)stream));
-    pmg_dev_free(h->ch_B);
-    h->ch_B     = NULL;
-    h->ch_B_cap = 0;
-    PMG_CALL(pmg_dev_alloc((void **)&h->ch_B, sizeof(double) * (size_t)F->ld * (size_t)C));
-    h->ch_B_cap = C;
-  }
+  if (bcs) PMG_CALL(pmg_devbuf_reserve(&h->ch_B, sizeof(double) * (size_t)F->ld * (size_t)C, stream));
   uint64_t *kh = (uint64_t *)malloc(sizeof(uint64_t) * (size_t)h->nlevels * (size_t)C);
   PMG_CHECK(kh, PMG_ERR_MEM, "out of host memory");
   for (int l = 0; l <= top; ++l)
@@ -201,35 +171,35 @@ static pmg_status mgmc_chains_run(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   const pmg_status kst = pmg_keybuf_set(&h->ch_keys, kh, (int64_t)h->nlevels * C, stream);
   free(kh);
   PMG_CALL(kst);
-  const uint64_t *keys = h->ch_keys.dev;
+  const uint64_t *keys = h->ch_keys.dev.p;
   const int32_t  *orig = pmg_mcsor_orig_dev(F->mc);
   const int64_t   nel  = F->ld * C;
-  const double   *btop = bcs ? h->ch_B : h->ch_bs;
+  const double   *btop = bcs ? h->ch_B.p : h->ch_bs.p;
   /* a top level with a low-rank update sweeps on a right-hand side the noise term can go onto: the library's copy of a per-chain
      B, or the shared b spread over ch_b[top] ONCE per call -- the term goes in and out bit for bit.  (The literal form's own cycles
      run on ch_b[top] = w, which then replaces the spread b: that one is needed for its = 0 with guesszero only.) */
   const int lrtop = chains_lrc(h, top) != NULL;
-  double   *bown  = !lrtop ? NULL : (bcs ? h->ch_B : h->ch_b[top]);
-  if (lrtop && !bcs && its > 0 && (!h->correction_form || guesszero)) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 0, h->ch_b[top], stream));
-  if (bcs) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 1, h->ch_B, stream));
-  else PMG_KERNEL(pmgk_permute_in(F->ld, orig, b_nat, h->ch_bs, stream));
-  PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, Y_nat, 1, h->ch_Y, stream));
+  double   *bown  = !lrtop ? NULL : (bcs ? h->ch_B.p : h->ch_b[top].p);
+  if (lrtop && !bcs && its > 0 && (!h->correction_form || guesszero)) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 0, h->ch_b[top].p, stream));
+  if (bcs) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 1, h->ch_B.p, stream));
+  else PMG_KERNEL(pmgk_permute_in(F->ld, orig, b_nat, h->ch_bs.p, stream));
+  PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, Y_nat, 1, h->ch_Y.p, stream));
   for (int32_t it = 0; it < its; ++it) {
     const uint64_t sample = counter0 + (uint64_t)it;
     if (!h->correction_form || (it == 0 && guesszero)) /* in place on (b, Y), pmg_mgmc_sample's default; or Y = MG(b) (src/pc_gamgmc.c:243-246) */
-      PMG_CALL(mg_vcycle_chains(h, C, keys, btop, bcs, bown, h->ch_Y, sample, !h->correction_form && !(it == 0 && guesszero), stream));
+      PMG_CALL(mg_vcycle_chains(h, C, keys, btop, bcs, bown, h->ch_Y.p, sample, !h->correction_form && !(it == 0 && guesszero), stream));
     else { /* w = b - A y; work = MG(w); y += work, src/pc_gamgmc.c:253-256 */
-      PMG_CALL(pmg_mcsor_residual_chains(F->mc, C, btop, bcs, h->ch_Y, h->ch_b[top], stream));
-      PMG_CALL(mg_vcycle_chains(h, C, keys, h->ch_b[top], 1, h->ch_b[top], h->ch_x[top], sample, 0, stream));
-      PMG_KERNEL(pmgk_axpy(nel, 1.0, h->ch_x[top], h->ch_Y, stream));
+      PMG_CALL(pmg_mcsor_residual_chains(F->mc, C, btop, bcs, h->ch_Y.p, h->ch_b[top].p, stream));
+      PMG_CALL(mg_vcycle_chains(h, C, keys, h->ch_b[top].p, 1, h->ch_b[top].p, h->ch_x[top].p, sample, 0, stream));
+      PMG_KERNEL(pmgk_axpy(nel, 1.0, h->ch_x[top].p, h->ch_Y.p, stream));
     }
     if (cb) {
-      PMG_KERNEL(pmgk_permute_out_chains(F->ld, orig, C, h->ch_Y, Y_nat, stream));
+      PMG_KERNEL(pmgk_permute_out_chains(F->ld, orig, C, h->ch_Y.p, Y_nat, stream));
       const int rc = cb(it, Y_nat, F->n, C, cbctx);
       PMG_CHECK(rc == 0, rc, "sample callback returned %d", rc);
     }
   }
-  PMG_KERNEL(pmgk_permute_out_chains(F->ld, orig, C, h->ch_Y, Y_nat, stream));
+  PMG_KERNEL(pmgk_permute_out_chains(F->ld, orig, C, h->ch_Y.p, Y_nat, stream));
   if (counter_out) *counter_out = counter0 + (uint64_t)its;
   return PMG_SUCCESS;
 }

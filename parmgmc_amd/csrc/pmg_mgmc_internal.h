@@ -98,16 +98,13 @@ struct pmg_mgmc_s {
   int       rb_fold;      /* lowest row-block level; the levels below are replicated on every rank */
   int32_t  *rb_fold_pos, *rb_fold_iota; /* device: layout position of natural row q of level rb_fold - 1, and 0, 1, 2, ... */
   double   *rb_fold_buf;                /* device: that level's vector in natural order (the all-gather buffer) */
-  /* multi-chain workspace (pmg_mgmc_sample_chains): allocated on first use, grows with the chain count */
-  int32_t    ch_cap;
-  double   **ch_b, **ch_x, **ch_r; /* [nlevels]: level vectors of ld x ch_cap doubles, chain fastest */
-  double    *ch_Y, *ch_bs;       /* the chains' iterate and the shared right-hand side in the finest level's layout */
-  double    *ch_xi, *ch_v;       /* exact coarse sampler: noise and L^-1 b + xi, n_0 x ch_cap */
-  pmg_keybuf ch_keys;            /* level_seed(seeds[c], l) at l * C + c */
-  double    *ch_B;               /* one right-hand side per chain in the finest level's layout (pmg_mgmc_sample_chains_rhs), ld x ch_B_cap */
-  int32_t    ch_B_cap;
-  double    *ch_eta;             /* the low-rank noise terms of one cycle: (directional sweeps of the levels with an update) x k x C */
-  int64_t    ch_eta_cap;         /* ... in doubles */
+  /* multi-chain workspace (pmg_mgmc_sample_chains): every buffer allocated on first use, grows with the chain count C */
+  pmg_devbuf *ch_b, *ch_x, *ch_r; /* [nlevels], one host array made by the first chains call: level vectors of ld x C doubles, chain fastest */
+  pmg_devbuf  ch_Y, ch_bs;        /* the chains' iterate and the shared right-hand side in the finest level's layout */
+  pmg_devbuf  ch_xi, ch_v;        /* exact coarse sampler: noise and L^-1 b + xi, n_0 x C */
+  pmg_keybuf  ch_keys;            /* level_seed(seeds[c], l) at l * C + c */
+  pmg_devbuf  ch_B;               /* one right-hand side per chain in the finest level's layout (pmg_mgmc_sample_chains_rhs), ld x C */
+  pmg_devbuf  ch_eta;             /* the low-rank noise terms of one cycle: (directional sweeps of the levels with an update) x k x C */
 };
 
 typedef struct {

@@ -24,9 +24,8 @@ struct pmg_woodbury_s {
   double  *S_sqrt, *wk, *partial; /* device: sqrt|S| (k), k-vector (k*k while T is formed), block sums */
   double   S[64];
   int      finished;
-  /* many chains (pmg_woodbury_*_chains): k x ch_cap k-vectors, the block sums of B^T Y and the chains' keys, first use */
-  int32_t    ch_cap;
-  double    *ch_wk, *ch_partial;
+  /* many chains (pmg_woodbury_*_chains): k x C k-vectors, the block sums of B^T Y and the chains' keys, first use */
+  pmg_devbuf ch_wk, ch_partial;
   pmg_keybuf ch_keys;
 };
 
@@ -35,7 +34,7 @@ pmg_status pmg_woodbury_destroy(pmg_woodbury *wp)
   if (!wp || !*wp) return PMG_SUCCESS;
   pmg_woodbury w = *wp;
   pmg_dev_free(w->B), pmg_dev_free(w->C), pmg_dev_free(w->G), pmg_dev_free(w->S_sqrt), pmg_dev_free(w->wk), pmg_dev_free(w->partial);
-  pmg_dev_free(w->ch_wk), pmg_dev_free(w->ch_partial), pmg_keybuf_free(&w->ch_keys);
+  pmg_devbuf_free(&w->ch_wk), pmg_devbuf_free(&w->ch_partial), pmg_keybuf_free(&w->ch_keys);
   free(w);
   *wp = NULL;
   return PMG_SUCCESS;
@@ -158,17 +157,9 @@ static pmg_status woodbury_chains_check(pmg_woodbury w, int32_t C)
 
 static pmg_status woodbury_chains_workspace(pmg_woodbury w, int32_t C, void *stream)
 {
-  if (C <= w->ch_cap) return PMG_SUCCESS;
-  PMG_HIP(hipStreamSynchronize((hipStream_t)stream)); /* the old buffers may still be in use */
-  pmg_dev_free(w->ch_wk);
-  pmg_dev_free(w->ch_partial);
-  w->ch_wk = w->ch_partial = NULL;
-  w->ch_cap                = 0;
-  const size_t kc = (size_t)w->k * (size_t)C;
-  PMG_CALL(pmg_dev_alloc((void **)&w->ch_wk, sizeof(double) * kc));
-  PMG_CALL(pmg_dev_alloc((void **)&w->ch_partial, sizeof(double) * kc * (size_t)pmgk_lrc_btx_chains_nblocks(w->n > 0 ? w->n : 1, 0)));
-  w->ch_cap = C;
-  return PMG_SUCCESS;
+  const size_t kc = sizeof(double) * (size_t)w->k * (size_t)C;
+  PMG_CALL(pmg_devbuf_reserve(&w->ch_wk, kc, stream));
+  return pmg_devbuf_reserve(&w->ch_partial, kc * (size_t)pmgk_lrc_btx_chains_nblocks(w->n > 0 ? w->n : 1, 0), stream);
 }
 
 /* W[:, c] = b + B (sqrt|S| o xi_c), xi_c the k row-stream normals of (seeds_host[c], counter): pmg_woodbury_noisy_rhs per chain
@@ -179,8 +170,8 @@ pmg_status pmg_woodbury_noisy_rhs_chains(pmg_woodbury w, int32_t C, const uint64
   PMG_CHECK(seeds_host && (w->n == 0 || (b_dev && W_dev)), PMG_ERR_ARG_NULL, "null argument");
   PMG_CALL(woodbury_chains_workspace(w, C, stream));
   PMG_CALL(pmg_keybuf_set(&w->ch_keys, seeds_host, C, stream));
-  PMG_KERNEL(pmgk_lrc_noise_chains(w->k, C, w->ch_keys.dev, 0, counter, w->S_sqrt, w->ch_wk, stream));
-  if (w->n) PMG_KERNEL(pmgk_lrc_axpy_chains(w->n, NULL, w->k, w->B, w->n, w->ch_wk, 1.0, b_dev, 0, W_dev, C, stream));
+  PMG_KERNEL(pmgk_lrc_noise_chains(w->k, C, w->ch_keys.dev.p, 0, counter, w->S_sqrt, w->ch_wk.p, stream));
+  if (w->n) PMG_KERNEL(pmgk_lrc_axpy_chains(w->n, NULL, w->k, w->B, w->n, w->ch_wk.p, 1.0, b_dev, 0, W_dev, C, stream));
   return PMG_SUCCESS;
 }
 
@@ -192,8 +183,8 @@ pmg_status pmg_woodbury_correct_chains(pmg_woodbury w, int32_t C, double *Y_dev,
   PMG_CHECK(w->finished, PMG_ERR_ARG_WRONGSTATE, "call pmg_woodbury_finish first");
   if (!w->n) return PMG_SUCCESS;
   PMG_CALL(woodbury_chains_workspace(w, C, stream));
-  PMG_KERNEL(pmgk_lrc_btx_chains(w->n, NULL, w->k, w->B, w->n, Y_dev, C, w->ch_partial, NULL, w->ch_wk, stream));
-  PMG_KERNEL(pmgk_lrc_axpy_chains(w->n, NULL, w->k, w->G, w->n, w->ch_wk, -1.0, Y_dev, 1, Y_dev, C, stream));
+  PMG_KERNEL(pmgk_lrc_btx_chains(w->n, NULL, w->k, w->B, w->n, Y_dev, C, w->ch_partial.p, NULL, w->ch_wk.p, stream));
+  PMG_KERNEL(pmgk_lrc_axpy_chains(w->n, NULL, w->k, w->G, w->n, w->ch_wk.p, -1.0, Y_dev, 1, Y_dev, C, stream));
   return PMG_SUCCESS;
 }
 
