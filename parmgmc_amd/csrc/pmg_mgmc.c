@@ -19,7 +19,8 @@
  * PMG_MG_FULL_GALERKIN and pmg_mgmc_set_keep_host.  z-slab hierarchies add a halo per sweep phase and fold into
  * replicated coarse levels.
  *
- * This file is the cycle: level_path decides the kernels of each level, mg_vcycle launches them,
+ * This file is the cycle: a level's kind (mg_kind, set once by the set-up) selects its sampler and residual, its transfer kind
+ * the restriction and prolongation; level_path decides what remains open from cycle to cycle, mg_vcycle launches them,
  * pmg_mgmc_get_algorithmic_bytes charges them, pmg_mgmc_sample runs the outer chain.  The hierarchy is built in
  * pmg_mgmc_setup.c (host sparse tools: pmg_hier_host.c); the multi-chain cycle is pmg_mgmc_chains.c, the single-kernel
  * diagnostics pmg_mgmc_level.c; pmg_mgmc_internal.h holds what they share.
@@ -28,12 +29,12 @@
 
 /* the phase-fused out-of-place sweep and the paired residual (kernels_stencil27_pair.hip) serve class-stencil levels
    that live on one device; PMG_ST27_PAIR=0 keeps the one-launch-per-colour kernels (same bits) */
-static int st27_use_pair(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR) && Lv->is_st27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz; }
+static int st27_use_pair(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR) && Lv->kind == MG_LV_ST27 && !Lv->distributed && Lv->kz0 == 0 && Lv->nzl == Lv->nz; }
 
 /* the same kernels on the z-slab of a distributed class-stencil level: one launch per z-parity phase instead of four, the
    halo of the boundary planes behind each as before; PMG_ST27_PAIR_SLAB=0 keeps the per-colour kernels (same bits; probes:
    2 = paired residual only, 3 = paired sweeps only) */
-static int st27_use_pair_slab(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR_SLAB) && Lv->is_st27 && Lv->distributed; }
+static int st27_use_pair_slab(const mg_level *Lv) { return pmg_switch(PMG_SW_ST27_PAIR_SLAB) && Lv->kind == MG_LV_ST27 && Lv->distributed; }
 
 /* the level's own iterate is swept out of place, into Lv->x2 */
 int pmg_mgmc_i_st27_out_of_place(const mg_level *Lv) { return Lv->x2 && st27_use_pair(Lv); }
@@ -85,9 +86,8 @@ pmg_status pmg_mgmc_i_halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stre
   const double *slo[2], *shi[2];
   double       *rlo[2], *rhi[2];
   int64_t       n[2];
-  int           nseg;
-  if (Lv->is_grid) { /* cvec: one block per colour */
-    nseg = 2;
+  switch (Lv->kind) {
+  case MG_LV_GRID_SLAB: /* cvec: one block per colour */
     for (int c = 0; c < 2; ++c) {
       int64_t own, ghost;
       PMG_CALL(pmg_grid_halo_plane(Lv->g, c, 0, &own, &ghost, &n[c]));
@@ -97,15 +97,20 @@ pmg_status pmg_mgmc_i_halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stre
       shi[c] = v + own;
       rhi[c] = v + ghost;
     }
-  } else {
-    nseg   = 1;
+    return pmg_dist_exchange(h->dist, 2, slo, n, rlo, n, shi, n, rhi, n, stream);
+  case MG_LV_ST27: /* padded natural order: one plane below, one above */
     n[0]   = Lv->off;
     slo[0] = v + Lv->off;
     rlo[0] = v;
     shi[0] = v + Lv->off * Lv->nzl;
     rhi[0] = v + Lv->off * ((int64_t)Lv->nzl + 1);
+    return pmg_dist_exchange(h->dist, 1, slo, n, rlo, n, shi, n, rhi, n, stream);
+  case MG_LV_EXACT:
+  case MG_LV_GRID:
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK: break; /* never z-slabs */
   }
-  return pmg_dist_exchange(h->dist, nseg, slo, n, rlo, n, shi, n, rhi, n, stream);
+  return PMG_SUCCESS;
 }
 
 /* `its` samples of a level sampler whose low-rank update is applied around the sweeps HERE (class-stencil levels, the grid
@@ -127,39 +132,51 @@ static pmg_status mg_one_sweep(void *ctx, int dir, const double *rhs, double *x,
   return a->sweep(a->h, a->Lv, dir, rhs, a->seed, a->ctr, stream);
 }
 
-static pmg_status mg_lowrank_sweeps(pmg_mgmc h, mg_level *Lv, int its, mg_dir_sweep sweep, uint64_t seed, uint64_t *ctr, void *stream)
+static pmg_status mg_lowrank_sweeps(pmg_mgmc h, int l, int its, mg_dir_sweep sweep, uint64_t seed, uint64_t *ctr, void *stream)
 {
+  mg_level      *Lv = &h->lv[l];
+  pmg_lrc        lr = mg_level_cycle_lrc(h, l);
   mg_sweep_args  a  = {h, Lv, sweep, seed, ctr};
   pmg_sweep_iter it = pmg_sweep_begin(h->sweep_type, its, 1, *ctr);
   while (pmg_sweep_next(&it)) {
-    PMG_CALL(pmg_lrc_dir_sweep(Lv->lrc, 1, it.dir, seed, *ctr, mg_one_sweep, &a, Lv->b, &Lv->x, stream)); /* an out-of-place sweep swaps Lv->x */
-    if (Lv->lrc) PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, Lv->x, stream)); /* the repair changed boundary planes */
+    PMG_CALL(pmg_lrc_dir_sweep(lr, 1, it.dir, seed, *ctr, mg_one_sweep, &a, Lv->b, &Lv->x, stream)); /* an out-of-place sweep swaps Lv->x */
+    if (lr) PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, Lv->x, stream)); /* the repair changed boundary planes */
   }
   return PMG_SUCCESS;
 }
 
 /* class-stencil level (same draw numbering as pmg_mcsor_sample_layout); on a z-slab the two z-parity phases of a sweep are
-   separated by a halo of the boundary planes */
-static pmg_status st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream)
+   separated by a halo of the boundary planes.  The set-up builds the levels' low-rank updates with the deterministic form */
+pmg_status pmg_mgmc_i_st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, int noisy, const double *rhs, double *y, uint64_t seed, uint64_t *ctr, void *stream)
 {
   const int backward = dir == PMG_SOR_BACKWARD_SWEEP;
   pmgk_st27 S        = Lv->st;
   S.sqrtdiag         = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;
+  if (!noisy) seed = 0;
+  const uint64_t draw = noisy ? *ctr : 0;
   if (!Lv->distributed) {
-    PMG_CALL(st27_one_sweep(Lv, &S, backward, h->omega, 1, seed, (*ctr)++, rhs, Lv->x_unset, stream));
-    Lv->x_unset = 0;
+    if (!noisy) PMG_KERNEL(pmgk_st27_sweep(&S, backward, h->omega, 0, seed, draw, rhs, y, stream));
+    else {
+      PMG_CALL(st27_one_sweep(Lv, &S, backward, h->omega, 1, seed, (*ctr)++, rhs, Lv->x_unset, stream));
+      Lv->x_unset = 0;
+    }
     return PMG_SUCCESS;
   }
-  const int pp  = Lv->x2 && st27_use_pair_slab(Lv) && pmg_switch(PMG_SW_ST27_PAIR_SLAB) != 2; /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
-  double   *out = pp ? Lv->x2 : Lv->x;
+  const int pp  = noisy && Lv->x2 && st27_use_pair_slab(Lv) && pmg_switch(PMG_SW_ST27_PAIR_SLAB) != 2; /* out of place: x2 <- sweep(x), phase by phase, then the buffers swap */
+  double   *out = !noisy ? y : (pp ? Lv->x2 : Lv->x);
   for (int phase = 0; phase < 2; ++phase) {
-    if (pp) PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, phase, h->omega, 1, seed, *ctr, rhs, Lv->x, out, stream));
-    else PMG_KERNEL(pmgk_st27_sweep_phase(&S, backward, phase, h->omega, 1, seed, *ctr, rhs, out, stream));
+    if (pp) PMG_KERNEL(pmgk_st27_sweep_pp_phase(&S, backward, phase, h->omega, 1, seed, draw, rhs, Lv->x, out, stream));
+    else PMG_KERNEL(pmgk_st27_sweep_phase(&S, backward, phase, h->omega, noisy, seed, draw, rhs, out, stream));
     PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, out, stream));
   }
-  ++*ctr;
+  if (noisy) ++*ctr;
   if (pp) st27_swap(Lv);
   return PMG_SUCCESS;
+}
+
+static pmg_status st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, const double *rhs, uint64_t seed, uint64_t *ctr, void *stream)
+{
+  return pmg_mgmc_i_st27_dir_sweep(h, Lv, dir, 1, rhs, NULL, seed, ctr, stream);
 }
 
 /* grid level of a z-slab hierarchy: one slab sweep (leaves the ghost planes current) */
@@ -180,28 +197,42 @@ static pmg_status mg_block_sweeps(pmg_mgmc h, mg_level *Lv, int its, uint64_t se
   return PMG_SUCCESS;
 }
 
-static pmg_status mg_smooth(pmg_mgmc h, int l, uint64_t seed, uint64_t *ctr, void *stream)
+/* one smoothing leg of level l on (Lv->b, Lv->x): `its` samples of the level's sampler (nu; coarse_its on level 0, where the exact
+   sampler draws its one sample whatever `its`).  The set-up's checks keep the grid and row-block kinds off level 0 */
+static pmg_status mg_smooth(pmg_mgmc h, int l, int its, uint64_t seed, uint64_t *ctr, void *stream)
 {
-  mg_level *Lv = &h->lv[l];
-  if (Lv->bg) PMG_CALL(mg_block_sweeps(h, Lv, h->nu, level_seed(seed, l), ctr, stream));
-  else if (Lv->is_grid && h->dist && Lv->lrc) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, slab_dir_sweep, level_seed(seed, l), ctr, stream)); /* MATLRC on z-slabs */
-  else if (Lv->is_grid && h->dist) PMG_CALL(pmg_dist_sample_cvec(h->dist, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* leaves the ghost planes current */
-  else if (Lv->is_grid) PMG_CALL(pmg_grid_sample_cvec(Lv->g, Lv->b, Lv->x, h->nu, h->scaled, level_seed(seed, l), *ctr, ctr, stream));
-  else if (Lv->is_st27) PMG_CALL(mg_lowrank_sweeps(h, Lv, h->nu, st27_dir_sweep, level_seed(seed, l), ctr, stream));
-  else if (Lv->dm) PMG_CALL(pmg_distmcsor_sample_layout(Lv->dm, Lv->b, Lv->x, h->nu, h->scaled, h->sweep_type, level_seed(seed, l), *ctr, ctr, stream)); /* row block: refreshes the ghost rows first, leaves them current */
-  else PMG_CALL(pmg_mcsor_sample_layout(Lv->mc, Lv->b, Lv->x, h->nu, h->scaled, level_seed(seed, l), *ctr, ctr, stream));
+  mg_level      *Lv  = &h->lv[l];
+  const uint64_t key = level_seed(seed, l);
+  switch (Lv->kind) {
+  case MG_LV_EXACT: return pmg_chol_sample(h->chol, Lv->b + Lv->off, Lv->x + Lv->off, 1, key, *ctr, stream);
+  case MG_LV_GRID: return pmg_grid_sample_cvec(Lv->g, Lv->b, Lv->x, its, h->scaled, key, *ctr, ctr, stream);
+  case MG_LV_GRID_SLAB:
+    if (mg_level_cycle_lrc(h, l)) return mg_lowrank_sweeps(h, l, its, slab_dir_sweep, key, ctr, stream);
+    return pmg_dist_sample_cvec(h->dist, Lv->b, Lv->x, its, h->scaled, h->sweep_type, key, *ctr, ctr, stream); /* leaves the ghost planes current */
+  case MG_LV_ST27: return mg_lowrank_sweeps(h, l, its, st27_dir_sweep, key, ctr, stream);
+  case MG_LV_SELL:
+    if (Lv->bg) return mg_block_sweeps(h, Lv, its, key, ctr, stream);
+    return pmg_mcsor_sample_layout(Lv->mc, Lv->b, Lv->x, its, h->scaled, key, *ctr, ctr, stream);
+  case MG_LV_ROWBLOCK: return pmg_distmcsor_sample_layout(Lv->dm, Lv->b, Lv->x, its, h->scaled, h->sweep_type, key, *ctr, ctr, stream); /* refreshes the ghost rows first, leaves them current */
+  }
   return PMG_SUCCESS;
 }
 
-/* r = b - A_l x by the level's residual kernel; the low-rank term of an update the LEVEL holds is the caller's */
+/* r = b - A_l x by the level's residual kernel; the low-rank term of an update the LEVEL holds (mg_level_cycle_lrc) is the caller's */
 static pmg_status mg_residual(mg_level *Lv, int pair, const double *b, const double *x, double *r, void *stream)
 {
-  if (Lv->is_grid) return pmg_grid_residual_cvec(Lv->g, b, x, r, stream);
-  if (Lv->is_st27 && pair) PMG_KERNEL(pmgk_st27_residual_pair(&Lv->st, b, x, r, stream));
-  else if (Lv->is_st27) PMG_KERNEL(pmgk_st27_residual(&Lv->st, b, x, r, stream));
-  else if (Lv->dm) return pmg_distmcsor_residual_layout(Lv->dm, b, x, r, stream); /* row block: + the all-reduced low-rank term */
-  else return pmg_mcsor_residual_layout(Lv->mc, b, x, r, stream);
-  return PMG_SUCCESS;
+  switch (Lv->kind) {
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB: return pmg_grid_residual_cvec(Lv->g, b, x, r, stream);
+  case MG_LV_ST27:
+    if (pair) PMG_KERNEL(pmgk_st27_residual_pair(&Lv->st, b, x, r, stream));
+    else PMG_KERNEL(pmgk_st27_residual(&Lv->st, b, x, r, stream));
+    return PMG_SUCCESS;
+  case MG_LV_SELL: return pmg_mcsor_residual_layout(Lv->mc, b, x, r, stream);
+  case MG_LV_ROWBLOCK: return pmg_distmcsor_residual_layout(Lv->dm, b, x, r, stream); /* + the all-reduced low-rank term */
+  case MG_LV_EXACT: break;
+  }
+  PMG_FAIL(PMG_ERR_PLIB, "an exactly sampled level has no residual kernel");
 }
 
 /* Level l distributed, level l - 1 replicated (the fold): a rank restricts into the coarse planes it owns -- CD becomes
@@ -238,22 +269,30 @@ pmg_status pmg_mgmc_i_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coar
   const int      fold = Lv->distributed && !Cc->distributed; /* distributed -> replicated */
   if (Lv->distributed) PMG_CALL(pmg_mgmc_i_halo_level(h, Lv, r_fine, stream));
   double *bc = fold ? fold_own_planes(h, l, &CD, b_coarse) : b_coarse;
-  if (Lv->grid_transfer) { /* matrix-free */
+  switch (Lv->transfer) {
+  case MG_TR_NONE: break;
+  case MG_TR_Q1_GRID: {
     pmgk_grid_layout GL;
     PMG_CALL(pmg_grid_get_kernel_layout(Lv->g, &GL));
     PMG_KERNEL(pmgk_q1_restrict(&GL, &CD, Lv->cpos_dev, r_fine, bc, stream));
-  } else if (Lv->nat_transfer) {
+    break;
+  }
+  case MG_TR_Q1_NAT: {
     const pmgk_st27_dims FD = level_dims(Lv);
     PMG_KERNEL(pmgk_st27_restrict(&FD, &CD, r_fine, bc, stream));
-  } else {
-    if (Lv->dm) PMG_CALL(pmg_distmcsor_refresh_layout(Lv->dm, r_fine, stream)); /* row block: the rows of P^T read r on other ranks' rows */
-    /* inside a cycle on one device the restriction also sets the zero guess of the coarse level: its rows are the rows of P^T, the
+    break;
+  }
+  case MG_TR_CSR: {
+    const int rowblock = Lv->kind == MG_LV_ROWBLOCK;
+    if (rowblock) PMG_CALL(pmg_distmcsor_refresh_layout(Lv->dm, r_fine, stream)); /* the rows of P^T read r on other ranks' rows */
+    /* inside a cycle on one device the restriction also sets the zero guess of a sliced-ELL coarse level: its rows are the rows of P^T, the
        padding of the layout is never written (zero since the allocation) -- one fill kernel less per level (PMG_MG_FUSED_ZERO=0) */
-    const int needs_zero = l - 1 >= 1 || h->coarse_type != 0;
-    double   *zero = pmg_switch(PMG_SW_MG_FUSED_ZERO) && needs_zero && !h->dist && !Lv->dm && !Cc->dm && b_coarse == Cc->b && Cc->mc && Lv->R_nrows == Cc->n ? Cc->x : NULL;
+    double *zero = pmg_switch(PMG_SW_MG_FUSED_ZERO) && !h->dist && !rowblock && Cc->kind == MG_LV_SELL && b_coarse == Cc->b && Lv->R_nrows == Cc->n ? Cc->x : NULL;
     PMG_KERNEL(pmgk_csr_spmv_rows(Lv->R_nrows, Lv->R_rowpos, Lv->R_rowptr, Lv->R_col, Lv->R_val, r_fine, b_coarse, 0, zero, stream));
     if (zero) Cc->x_zeroed = 1;
-    if (Lv->dm && l == h->rb_fold) PMG_CALL(pmg_mgmc_i_rb_fold_allgather(h, b_coarse, stream)); /* the replicated level below: every rank needs the whole right-hand side */
+    if (rowblock && l == h->rb_fold) PMG_CALL(pmg_mgmc_i_rb_fold_allgather(h, b_coarse, stream)); /* the replicated level below: every rank needs the whole right-hand side */
+    break;
+  }
   }
   if (fold) PMG_CALL(fold_allgather(h, l, b_coarse, stream));
   return PMG_SUCCESS;
@@ -285,7 +324,7 @@ static pmg_status mg_residual_restrict_slab(pmg_mgmc h, int l, void *stream)
   int     done = 0;
   PMG_CALL(pmg_grid_residual_restrict(Lv->g, Lv->b, Lv->x, Lv->kz0 > 0 ? Lv->y2lo : NULL, Lv->kz0 + Lv->nzl < Lv->nz ? Lv->y2hi : NULL, &CD, bc, &done, stream));
   PMG_CHECK(done, PMG_ERR_PLIB, "level %d: the fused residual + restriction refused a slab the set-up had accepted", l);
-  if (Lv->lrc) PMG_CALL(pmg_lrc_residual_sub_restricted(Lv->lrc, Cc->lrc, Lv->x, Cc->b, stream)); /* - P^T B S B^T x = - B_{l-1} (S B^T x); B^T x summed over the ranks */
+  if (mg_level_cycle_lrc(h, l)) PMG_CALL(pmg_lrc_residual_sub_restricted(mg_level_cycle_lrc(h, l), mg_level_cycle_lrc(h, l - 1), Lv->x, Cc->b, stream)); /* - P^T B S B^T x = - B_{l-1} (S B^T x); B^T x summed over the ranks */
   if (fold) PMG_CALL(fold_allgather(h, l, Cc->b, stream));
   return PMG_SUCCESS;
 }
@@ -297,16 +336,17 @@ pmg_status pmg_mgmc_i_prolong_add(pmg_mgmc h, int l, const double *e_coarse, dou
   /* a z-slab also interpolates onto its in-domain ghost planes (from its coarse planes + coarse ghost planes): the
      same arithmetic the owner does, so the fine ghost planes stay current without an exchange */
   const int glo = Lv->distributed && Lv->kz0 > 0, ghi = Lv->distributed && Lv->kz0 + Lv->nzl < Lv->nz;
-  if (Lv->grid_transfer) { /* matrix-free */
-    pmgk_grid_layout     GL;
-    const pmgk_st27_dims CD = level_dims(Cc);
+  const pmgk_st27_dims FD = level_dims(Lv), CD = level_dims(Cc);
+  switch (Lv->transfer) {
+  case MG_TR_NONE: break;
+  case MG_TR_Q1_GRID: {
+    pmgk_grid_layout GL;
     PMG_CALL(pmg_grid_get_kernel_layout(Lv->g, &GL));
     PMG_KERNEL(pmgk_q1_prolong_add(&GL, &CD, Lv->cpos_dev, -glo, Lv->nzl + glo + ghi, only_color, e_coarse, x_fine, stream));
-  } else if (Lv->nat_transfer) {
-    const pmgk_st27_dims FD = level_dims(Lv), CD = level_dims(Cc);
-    PMG_KERNEL(pmgk_st27_prolong_add(&FD, &CD, Lv->kz0 - glo, Lv->nzl + glo + ghi, e_coarse, x_fine, stream));
-  } else {
-    PMG_KERNEL(pmgk_csr_spmv_rows(Lv->P_nrows, Lv->P_rowpos, Lv->P_rowptr, Lv->P_col, Lv->P_val, e_coarse, x_fine, 1, NULL, stream));
+    break;
+  }
+  case MG_TR_Q1_NAT: PMG_KERNEL(pmgk_st27_prolong_add(&FD, &CD, Lv->kz0 - glo, Lv->nzl + glo + ghi, e_coarse, x_fine, stream)); break;
+  case MG_TR_CSR: PMG_KERNEL(pmgk_csr_spmv_rows(Lv->P_nrows, Lv->P_rowpos, Lv->P_rowptr, Lv->P_col, Lv->P_val, e_coarse, x_fine, 1, NULL, stream)); break;
   }
   return PMG_SUCCESS;
 }
@@ -327,8 +367,7 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
   int       first[64], count[64], nslots = 0;
   pmg_lrc   any = NULL;
   for (int l = 0; l <= top; ++l) {
-    mg_level *Lv = &h->lv[l];
-    pmg_lrc   lr = mg_level_lrc(Lv);
+    pmg_lrc lr = mg_level_path_lrc(h, l);
     first[l] = count[l] = 0;
     if (!lr) continue;
     pmg_lrc_preset_eta(lr, 0, 0, 0, NULL, 0); /* forget the last cycle's */
@@ -348,7 +387,7 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
   if (!h->eta_batch) PMG_CALL(pmg_dev_alloc((void **)&h->eta_batch, sizeof(double) * MG_ETA_STRIDE * PMGK_NORMAL_BATCH_MAX));
   PMG_KERNEL(pmgk_fill_normal_batch(nslots, pmg_lrc_rank(any), seeds, ctrs, pmg_lrc_sqrtS(any), h->eta_batch, MG_ETA_STRIDE, stream)); /* S is the same on every level (src/pc_gamgmc.c:170-176) */
   for (int l = 0; l <= top; ++l)
-    if (count[l]) pmg_lrc_preset_eta(mg_level_lrc(&h->lv[l]), level_seed(seed, l), ctr[l], count[l], h->eta_batch + (size_t)first[l] * MG_ETA_STRIDE, MG_ETA_STRIDE);
+    if (count[l]) pmg_lrc_preset_eta(mg_level_path_lrc(h, l), level_seed(seed, l), ctr[l], count[l], h->eta_batch + (size_t)first[l] * MG_ETA_STRIDE, MG_ETA_STRIDE);
   return PMG_SUCCESS;
 }
 
@@ -358,7 +397,7 @@ static pmg_status mg_draw_lowrank_noise(pmg_mgmc h, uint64_t seed, const uint64_
 enum { MG_GUESS_KEEP, MG_GUESS_FILL, MG_GUESS_UNSET };  /* the iterate a level starts from: its own | zero, stored by a fill kernel (or by the CSR restriction into it, x_zeroed) | zero, NOT stored: the first out-of-place sweep is told */
 enum { MG_RR_TWO, MG_RR_FUSED, MG_RR_FUSED_SLAB };      /* residual, then restriction | b_{l-1} = P^T (b - A x) in one pass on one device | the same on a z-slab */
 typedef struct {
-  pmg_lrc lrc;                   /* the low-rank update the level's sampler applies, NULL if none */
+  pmg_lrc lrc;                   /* mg_level_path_lrc: the low-rank update the level's sampler applies with the cycle's help, NULL if none */
   double  rows;                  /* owned unknowns */
   int     zero_guess;            /* MG_GUESS_* (level 0: in front of the Gibbs sweeps; the exact sampler takes no guess) */
   int     rr;                    /* MG_RR_*, l >= 1 */
@@ -370,23 +409,23 @@ typedef struct {
 static mg_path level_path(const struct pmg_mgmc_s *h, int l, int top_has_guess)
 {
   const mg_level *Lv = &h->lv[l];
-  mg_path         p  = {mg_level_lrc(Lv), level_rows(Lv), MG_GUESS_FILL, MG_RR_TWO, 0, 0, -1};
+  mg_path         p  = {mg_level_path_lrc(h, l), level_rows(Lv), MG_GUESS_FILL, MG_RR_TWO, 0, 0, -1};
   if (l == 0 ? h->coarse_type == 0 : (l == h->nlevels - 1 && top_has_guess)) p.zero_guess = MG_GUESS_KEEP;
   else if (l >= 1 && pmg_mgmc_i_st27_out_of_place(Lv) && h->nu >= 1) p.zero_guess = MG_GUESS_UNSET; /* (also under a low-rank update: the noise term changes b, the repair acts on the swept iterate) */
   p.residual_pair = st27_use_pair(Lv) || (st27_use_pair_slab(Lv) && pmg_switch(PMG_SW_ST27_PAIR_SLAB) != 3);
   if (l == 0) return p;
   const mg_level *Cc = &h->lv[l - 1];
-  if (Lv->is_grid && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused) {
+  if (Lv->transfer == MG_TR_Q1_GRID && !Lv->cpos_dev && !h->no_fused) {
     /* z-slab: agreed by the ranks at set-up, and b's ghost planes are current in the in-place form only (pmg_mgmc_sample).
        One device: a local update on both levels and the kernel's own gate, which the launcher asks first as well */
     const pmgk_st27_dims CD = level_dims(Cc);
     if (Lv->distributed) p.rr = Lv->rr_slab && !h->correction_form ? MG_RR_FUSED_SLAB : MG_RR_TWO;
-    else if ((!p.lrc || (pmg_lrc_is_local(p.lrc) && Cc->is_st27 && pmg_lrc_is_local(Cc->lrc))) && pmg_grid_residual_restrict_applies(Lv->g, &CD, 0, 0)) p.rr = MG_RR_FUSED;
+    else if ((!p.lrc || (pmg_lrc_is_local(p.lrc) && Cc->kind == MG_LV_ST27 && pmg_lrc_is_local(mg_level_cycle_lrc(h, l - 1)))) && pmg_grid_residual_restrict_applies(Lv->g, &CD, 0, 0)) p.rr = MG_RR_FUSED;
   }
   p.rr_lowrank_restricted = p.rr != MG_RR_TWO && p.lrc;
   /* with omega = 1 a colour sweep never reads the old values of the colour it updates (the (1-omega) x term is
      gone), so the colour the post-smoother visits first needs no correction: it is overwritten unread */
-  if (Lv->grid_transfer && h->omega == 1.0 && h->nu >= 1 && !pmg_switch(PMG_SW_MG_PROLONG_BOTH)) p.prolong_colour = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 0 : 1;
+  if (Lv->transfer == MG_TR_Q1_GRID && h->omega == 1.0 && h->nu >= 1 && !pmg_switch(PMG_SW_MG_PROLONG_BOTH)) p.prolong_colour = h->sweep_type == PMG_SOR_BACKWARD_SWEEP ? 0 : 1;
   return p;
 }
 
@@ -423,7 +462,7 @@ static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_
     const mg_path *p  = &path[l];
     PMG_CALL(mg_zero_guess(Lv, p->zero_guess, stream));
     pmg_lrc_expect_residual(p->lrc, 1); /* the last repair of the pre-smoothing also starts the residual's low-rank term */
-    const pmg_status sst = mg_smooth(h, l, seed, &ctr[l], stream);
+    const pmg_status sst = mg_smooth(h, l, h->nu, seed, &ctr[l], stream);
     pmg_lrc_expect_residual(p->lrc, sst == PMG_SUCCESS); /* (an error: forget) */
     PMG_CALL(sst);
     switch (p->rr) {
@@ -432,28 +471,22 @@ static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_
       int                  done = 0;
       PMG_CALL(pmg_grid_residual_restrict(Lv->g, Lv->b, Lv->x, NULL, NULL, &CD, Cc->b, &done, stream));
       PMG_CHECK(done, PMG_ERR_PLIB, "level %d: the fused residual + restriction refused a level its own gate had accepted", l);
-      if (p->rr_lowrank_restricted) PMG_CALL(pmg_lrc_residual_sub_restricted(p->lrc, Cc->lrc, Lv->x, Cc->b, stream));
+      if (p->rr_lowrank_restricted) PMG_CALL(pmg_lrc_residual_sub_restricted(p->lrc, mg_level_cycle_lrc(h, l - 1), Lv->x, Cc->b, stream));
       break;
     }
     case MG_RR_FUSED_SLAB: PMG_CALL(mg_residual_restrict_slab(h, l, stream)); break;
     default:
       PMG_CALL(mg_residual(Lv, p->residual_pair, Lv->b, Lv->x, Lv->r, stream));
-      if (Lv->lrc) PMG_CALL(pmg_lrc_residual_sub(Lv->lrc, Lv->x, Lv->r, stream)); /* PCMGSetResidual(..., As[l]), src/pc_gamgmc.c:194; class-stencil levels and the grid level of a z-slab hierarchy: held here, not in the grid object */
+      if (mg_level_cycle_lrc(h, l)) PMG_CALL(pmg_lrc_residual_sub(mg_level_cycle_lrc(h, l), Lv->x, Lv->r, stream)); /* PCMGSetResidual(..., As[l]), src/pc_gamgmc.c:194 */
       PMG_CALL(pmg_mgmc_i_restrict(h, l, Lv->r, Cc->b, stream));
     }
   }
-  {
-    mg_level *C0 = &h->lv[0];
-    PMG_CALL(mg_zero_guess(C0, path[0].zero_guess, stream));
-    if (h->coarse_type == 0) PMG_CALL(pmg_chol_sample(h->chol, C0->b + C0->off, C0->x + C0->off, 1, level_seed(seed, 0), ctr[0], stream));
-    else if (C0->bg) PMG_CALL(mg_block_sweeps(h, C0, h->coarse_its, level_seed(seed, 0), &ctr[0], stream));
-    else if (C0->is_st27) PMG_CALL(mg_lowrank_sweeps(h, C0, h->coarse_its, st27_dir_sweep, level_seed(seed, 0), &ctr[0], stream));
-    else PMG_CALL(pmg_mcsor_sample_layout(C0->mc, C0->b, C0->x, h->coarse_its, h->scaled, level_seed(seed, 0), ctr[0], &ctr[0], stream));
-  }
+  PMG_CALL(mg_zero_guess(&h->lv[0], path[0].zero_guess, stream));
+  PMG_CALL(mg_smooth(h, 0, h->coarse_its, seed, &ctr[0], stream));
   for (int l = 1; l <= top; ++l) {
     PMG_CALL(pmg_mgmc_i_prolong_add(h, l, h->lv[l - 1].x, h->lv[l].x, path[l].prolong_colour, stream));
     pmg_lrc_expect_residual(path[l].lrc, 0); /* no residual behind the post-smoothing */
-    PMG_CALL(mg_smooth(h, l, seed, &ctr[l], stream));
+    PMG_CALL(mg_smooth(h, l, h->nu, seed, &ctr[l], stream));
   }
   if (h->lrc_k > 0) PMG_CALL(mg_draw_lowrank_noise(h, seed, ctr, 0, stream)); /* nothing outside this cycle takes its noise terms */
   return PMG_SUCCESS;
@@ -477,6 +510,27 @@ static pmg_status mg_vcycle(pmg_mgmc h, uint64_t seed, uint64_t sample, int top_
                                           residual term (8 k + 8) ns + (8 k + 16) ns' (ns' = ns unrestricted, coarse rows restricted)
    per_level (may be NULL): nlevels entries, the smoothing / residual / transfer bytes charged to the level they run on
    (a transfer is charged to its FINE level). */
+static pmg_status level_kernel_bytes(const struct pmg_mgmc_s *h, const mg_level *Lv, double N, double Nc, double *sweep /* one directional sweep */, double *rr_two /* residual, then restriction */)
+{
+  *sweep = *rr_two = 0.0;
+  switch (Lv->kind) {
+  case MG_LV_EXACT: break; /* no sweeps: 8 N^2 */
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB:
+  case MG_LV_ST27:
+    *sweep  = (Lv->kind == MG_LV_ST27 || h->omega == 1.0 ? 24.0 : 32.0) * N;
+    *rr_two = 24.0 * N + 8.0 * N + 8.0 * Nc;
+    break;
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK:
+    *sweep  = 12.0 * (double)Lv->A_nnz + 40.0 * N;
+    *rr_two = 12.0 * (double)Lv->A_nnz + 28.0 * N + 12.0 * (double)Lv->P_nnz + 12.0 * Nc + 8.0 * N;
+    if (Lv->bg) return pmg_blockgibbs_get_algorithmic_bytes(Lv->bg, sweep);
+    break;
+  }
+  return PMG_SUCCESS;
+}
+
 pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per_level)
 {
   PMG_CHECK(h && total, PMG_ERR_ARG_NULL, "null argument");
@@ -493,26 +547,27 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
     /* a rank whose slab or block misses B's support launches none of the low-rank kernels: ns = 0, no bytes */
     if (p.lrc) pmg_lrc_get_sizes(p.lrc, &k, &ns, &lr_dense);
     if (lr_dense) ns = (int64_t)N; /* dense factors: every row of the level */
-    double       bgsweep = 0.0;
-    if (Lv->bg) PMG_CALL(pmg_blockgibbs_get_algorithmic_bytes(Lv->bg, &bgsweep));
-    const double sweep = Lv->bg ? bgsweep : Lv->is_grid ? (h->omega == 1.0 ? 24.0 : 32.0) * N : (Lv->is_st27 ? 24.0 * N : 12.0 * (double)Lv->A_nnz + 40.0 * N);
+    const double Nc = l >= 1 ? level_rows(&h->lv[l - 1]) : 0.0;
+    double       sweep, rr_two;
+    PMG_CALL(level_kernel_bytes(h, Lv, N, Nc, &sweep, &rr_two));
     const double lrsw  = p.lrc ? ((8.0 * k + 24.0) + (16.0 * k + 24.0)) * (double)ns : 0.0;
     const double lrres = p.lrc ? (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)ns : 0.0; /* unrestricted residual term */
     double       by    = p.zero_guess == MG_GUESS_FILL ? 8.0 * N : (p.zero_guess == MG_GUESS_UNSET ? -8.0 * N : 0.0); /* the zero fill / the first sweep does not read x */
     if (l == 0) {
-      by += h->coarse_type == 0 ? 8.0 * N * N : pmg_mgmc_i_level_sweeps(h, l) * (sweep + lrsw);
+      by += Lv->kind == MG_LV_EXACT ? 8.0 * N * N : pmg_mgmc_i_level_sweeps(h, l) * (sweep + lrsw);
     } else {
-      const mg_level *Cc = &h->lv[l - 1];
-      const double    Nc = level_rows(Cc);
+      const pmg_lrc clr = p.rr_lowrank_restricted ? mg_level_cycle_lrc(h, l - 1) : NULL; /* the coarse update the restricted residual term runs over */
       by += pmg_mgmc_i_level_sweeps(h, l) * (sweep + lrsw);
-      if (p.rr != MG_RR_TWO) by += 16.0 * N + 8.0 * Nc;
-      else if (Lv->is_grid || Lv->is_st27) by += 24.0 * N + 8.0 * N + 8.0 * Nc;
-      else by += 12.0 * (double)Lv->A_nnz + 28.0 * N + 12.0 * (double)Lv->P_nnz + 12.0 * Nc + 8.0 * N;
-      if (p.rr_lowrank_restricted && Cc->lrc) pmg_lrc_get_sizes(Cc->lrc, &kc, &nc, &cdense);
-      if (p.rr_lowrank_restricted && Cc->lrc && !cdense) by += (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)nc;
+      by += p.rr != MG_RR_TWO ? 16.0 * N + 8.0 * Nc : rr_two;
+      if (clr) pmg_lrc_get_sizes(clr, &kc, &nc, &cdense);
+      if (clr && !cdense) by += (8.0 * k + 8.0) * (double)ns + (8.0 * k + 16.0) * (double)nc;
       else by += lrres;
-      if (Lv->grid_transfer || Lv->nat_transfer) by += (p.prolong_colour >= 0 ? 8.0 : 16.0) * N + 8.0 * Nc;
-      else by += 12.0 * (double)Lv->P_nnz + 20.0 * N + 8.0 * Nc;
+      switch (Lv->transfer) {
+      case MG_TR_NONE: break;
+      case MG_TR_Q1_GRID:
+      case MG_TR_Q1_NAT: by += (p.prolong_colour >= 0 ? 8.0 : 16.0) * N + 8.0 * Nc; break;
+      case MG_TR_CSR: by += 12.0 * (double)Lv->P_nnz + 20.0 * N + 8.0 * Nc; break;
+      }
       if (l == top && h->correction_form) by += 48.0 * N + lrres;
     }
     if (per_level) per_level[l] = by;
@@ -521,13 +576,18 @@ pmg_status pmg_mgmc_get_algorithmic_bytes(pmg_mgmc h, double *total, double *per
   return PMG_SUCCESS;
 }
 
-static pmg_status lvl_to_layout(mg_level *Lv, const double *nat, double *lay, void *stream)
+/* the caller's vector of the finest level into (to = 1) or out of the level's layout */
+static pmg_status lvl_permute(mg_level *Lv, int to, const double *in, double *out, void *stream)
 {
-  return Lv->is_grid ? pmg_grid_to_cvec(Lv->g, nat, lay, stream) : pmg_mcsor_to_layout(Lv->mc, nat, lay, stream);
-}
-static pmg_status lvl_from_layout(mg_level *Lv, const double *lay, double *nat, void *stream)
-{
-  return Lv->is_grid ? pmg_grid_from_cvec(Lv->g, lay, nat, stream) : pmg_mcsor_from_layout(Lv->mc, lay, nat, stream);
+  switch (Lv->kind) {
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB: return to ? pmg_grid_to_cvec(Lv->g, in, out, stream) : pmg_grid_from_cvec(Lv->g, in, out, stream);
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK: return to ? pmg_mcsor_to_layout(Lv->mc, in, out, stream) : pmg_mcsor_from_layout(Lv->mc, in, out, stream);
+  case MG_LV_ST27:
+  case MG_LV_EXACT: break;
+  }
+  PMG_FAIL(PMG_ERR_PLIB, "the finest level is a grid or a sliced-ELL level");
 }
 
 pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32_t its, int guesszero, uint64_t seed, uint64_t counter0, uint64_t *counter_out, pmg_sample_callback cb, void *cbctx, void *stream)
@@ -537,11 +597,11 @@ pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32
   PMG_CHECK(its >= 0, PMG_ERR_ARG_OUTOFRANGE, "its = %d", its);
   mg_level    *F     = &h->lv[h->nlevels - 1];
   const size_t bytes = sizeof(double) * (size_t)F->ld;
-  PMG_CALL(lvl_to_layout(F, b_nat, h->b_lay, stream));
-  PMG_CALL(lvl_to_layout(F, y_nat, h->y_lay, stream));
+  PMG_CALL(lvl_permute(F, 1, b_nat, h->b_lay, stream));
+  PMG_CALL(lvl_permute(F, 1, y_nat, h->y_lay, stream));
   if (h->correction_form && F->distributed) PMG_CALL(pmg_mgmc_i_halo_level(h, F, h->y_lay, stream)); /* the outer residual reads the ghost planes of y */
   if (level_path(h, h->nlevels - 1, 1).rr == MG_RR_FUSED_SLAB) PMG_CALL(pmg_mgmc_i_halo_level(h, F, h->b_lay, stream)); /* the fused residual + restriction reads b on the ghost planes */
-  if (h->correction_form && F->dm) PMG_CALL(pmg_distmcsor_refresh_layout(F->dm, h->y_lay, stream)); /* ... the ghost rows of a row block */
+  if (h->correction_form && F->kind == MG_LV_ROWBLOCK) PMG_CALL(pmg_distmcsor_refresh_layout(F->dm, h->y_lay, stream)); /* ... the ghost rows of a row block */
   for (int32_t it = 0; it < its; ++it) {
     if (!h->correction_form) {
       /* The cycle run IN PLACE on (b, y): a stationary linear sweep satisfies S(b, y) = y + S(b - A y, 0) with the
@@ -561,18 +621,18 @@ pmg_status pmg_mgmc_sample(pmg_mgmc h, const double *b_nat, double *y_nat, int32
       PMG_HIP(hipMemcpyAsync(h->y_lay, F->x, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     } else { /* w = b - A y; work = MG(w); y += work, src/pc_gamgmc.c:253-256 */
       PMG_CALL(mg_residual(F, 0, h->b_lay, h->y_lay, F->b, stream));
-      if (F->lrc) PMG_CALL(pmg_lrc_residual_sub(F->lrc, h->y_lay, F->b, stream)); /* z-slabs */
+      if (mg_level_cycle_lrc(h, h->nlevels - 1)) PMG_CALL(pmg_lrc_residual_sub(mg_level_cycle_lrc(h, h->nlevels - 1), h->y_lay, F->b, stream)); /* z-slabs */
       PMG_CALL(mg_vcycle(h, seed, counter0 + (uint64_t)it, 0, stream));
       PMG_KERNEL(pmgk_axpy(F->ld, 1.0, F->x, h->y_lay, stream));
     }
     if (cb) { /* pg->scb(it, y, ctx), src/pc_gamgmc.c:258 */
-      PMG_CALL(lvl_from_layout(F, h->y_lay, y_nat, stream));
+      PMG_CALL(lvl_permute(F, 0, h->y_lay, y_nat, stream));
       const int rc = cb(it, y_nat, h->n_io, cbctx);
       if (rc != 0 && counter_out) *counter_out = counter0 + (uint64_t)it + 1; /* y holds sample it: a resumed chain draws the next noise */
       PMG_CHECK(rc == 0, rc, "sample callback returned %d", rc);
     }
   }
-  PMG_CALL(lvl_from_layout(F, h->y_lay, y_nat, stream));
+  PMG_CALL(lvl_permute(F, 0, h->y_lay, y_nat, stream));
   if (counter_out) *counter_out = counter0 + (uint64_t)its;
   return PMG_SUCCESS;
 }

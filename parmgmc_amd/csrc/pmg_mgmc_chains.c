@@ -9,10 +9,6 @@
    of a cycle are drawn by one launch; every such right-hand side is the cycle's own and takes the term in place (pmg_lrc.c). */
 #include "pmg_mgmc_internal.h"
 
-/* the update the chains cycle applies on level l: the level's MCSOR object holds it; none on an exactly sampled coarsest level,
-   whose factor is that of the explicit sum */
-static pmg_lrc chains_lrc(const struct pmg_mgmc_s *h, int l) { return h->lv[l].mc && !(l == 0 && h->coarse_type == 0) ? pmg_mcsor_lrc(h->lv[l].mc) : NULL; }
-
 void pmg_mgmc_i_free_chains(pmg_mgmc h)
 {
   for (int l = 0; l < 3 * h->nlevels && h->ch_b; ++l) pmg_devbuf_free(&h->ch_b[l]); /* ch_b, ch_x, ch_r: one array (mgmc_chains_workspace) */
@@ -60,7 +56,7 @@ static pmg_status chains_draw_lowrank_noise(pmg_mgmc h, int32_t C, const uint64_
   int                 nslots = 0;
   plan.n = 0;
   for (int l = 0; l < h->nlevels; ++l) {
-    pmg_lrc   lr = chains_lrc(h, l);
+    pmg_lrc   lr = mg_level_sampler_lrc(h, l);
     const int n  = pmg_mgmc_i_level_sweeps(h, l);
     first[l]     = nslots;
     if (!lr || n <= 0) continue;
@@ -83,7 +79,7 @@ static pmg_status chains_draw_lowrank_noise(pmg_mgmc h, int32_t C, const uint64_
 static pmg_status chains_smooth(pmg_mgmc h, int l, int32_t C, const uint64_t *keys, int its, uint64_t *ctr, int first, int *done, const double *b, int bcs, double *bown, double *x, void *stream)
 {
   mg_level *Lv = &h->lv[l];
-  pmg_lrc   lr = chains_lrc(h, l);
+  pmg_lrc   lr = mg_level_sampler_lrc(h, l);
   if (!lr) return pmg_mcsor_sweeps_chains(Lv->mc, C, keys + (size_t)l * C, 1, h->scaled, its, *ctr, ctr, b, bcs, x, stream);
   const int64_t kc = (int64_t)pmg_lrc_rank(lr) * C;
   PMG_CALL(pmg_mcsor_sweeps_lowrank_chains(Lv->mc, C, keys + (size_t)l * C, h->scaled, its, *ctr, ctr, (const double *)h->ch_eta.p + (int64_t)(first + *done) * kc, kc, bown, x, stream));
@@ -145,8 +141,8 @@ static pmg_status mgmc_chains_check(pmg_mgmc h, int32_t C)
   PMG_CHECK(h->is_setup, PMG_ERR_ARG_WRONGSTATE, "call pmg_mgmc_setup first");
   for (int l = 0; l < h->nlevels; ++l) {
     const mg_level *Lv = &h->lv[l];
-    PMG_CHECK(!Lv->dm && !Lv->is_grid && !Lv->is_st27 && (Lv->mc || (l == 0 && h->coarse_type == 0)), PMG_ERR_SUP, "level %d is not a sliced-ELL level: not supported by the multi-chain cycle", l);
-    if (Lv->mc) PMG_CALL(pmg_mcsor_chains_supported(Lv->mc));
+    PMG_CHECK(Lv->kind == MG_LV_SELL || Lv->kind == MG_LV_EXACT, PMG_ERR_SUP, "level %d is not a sliced-ELL level: not supported by the multi-chain cycle", l);
+    if (Lv->kind == MG_LV_SELL) PMG_CALL(pmg_mcsor_chains_supported(Lv->mc));
     PMG_CALL(pmg_chains_size_check(Lv->ld, C));
   }
   return PMG_SUCCESS;
@@ -178,7 +174,7 @@ static pmg_status mgmc_chains_run(pmg_mgmc h, int32_t C, const uint64_t *seeds, 
   /* a top level with a low-rank update sweeps on a right-hand side the noise term can go onto: the library's copy of a per-chain
      B, or the shared b spread over ch_b[top] ONCE per call -- the term goes in and out bit for bit.  (The literal form's own cycles
      run on ch_b[top] = w, which then replaces the spread b: that one is needed for its = 0 with guesszero only.) */
-  const int lrtop = chains_lrc(h, top) != NULL;
+  const int lrtop = mg_level_sampler_lrc(h, top) != NULL;
   double   *bown  = !lrtop ? NULL : (bcs ? h->ch_B.p : h->ch_b[top].p);
   if (lrtop && !bcs && its > 0 && (!h->correction_form || guesszero)) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 0, h->ch_b[top].p, stream));
   if (bcs) PMG_KERNEL(pmgk_permute_in_chains(F->ld, orig, C, b_nat, 1, h->ch_B.p, stream));
@@ -247,7 +243,7 @@ pmg_status pmg_mgmc_sample_chains_rhs(pmg_mgmc h, int32_t C, const uint64_t *see
    per-chain-b sweep (+ 8 N C - 8 N); spreading b is once per call, not per cycle, and not counted. */
 static double chains_lowrank_bytes(pmg_mgmc h, int l, double Cd)
 {
-  pmg_lrc lr = chains_lrc(h, l);
+  pmg_lrc lr = mg_level_sampler_lrc(h, l);
   if (!lr) return 0.0;
   const int top = h->nlevels - 1;
   int32_t   k;

@@ -5,6 +5,11 @@
  *   pmg_mgmc.c         the V-cycle, its byte model and pmg_mgmc_sample
  *   pmg_mgmc_chains.c  the multi-chain cycle
  *   pmg_mgmc_level.c   single-kernel entry points of one level (diagnostics)
+ * A level has ONE kind (mg_kind: which sampler and residual it runs, who holds its low-rank update, how its vectors are laid
+ * out) and ONE transfer kind (mg_transfer: how it restricts into and interpolates from the next coarser level).  The set-up
+ * assigns both, once; every dispatch on them is a switch without a default, so that -Wswitch names the place a new kind
+ * forgets.  What the caller hands in before set-up (mg_level_in, h->in) is apart from what the cycle reads afterwards
+ * (mg_level, h->lv) and is released when the set-up has succeeded.
  * Everything declared here is internal to the library: PMG_HIDDEN keeps it out of the exported symbols. */
 #ifndef PMG_MGMC_INTERNAL_H
 #define PMG_MGMC_INTERNAL_H
@@ -19,13 +24,29 @@ typedef struct {
   double  *v;
 } hcsr;
 
+/* kind of a level          sampler (mg_smooth)                    residual (mg_residual)          low-rank update held by        vectors
+   MG_LV_EXACT      pmg_chol_sample (coarsest, Cholesky)   none                            the factored sum                natural order: padded (DMDA), ld = n (caller's)
+   MG_LV_GRID       pmg_grid_sample_cvec                   pmg_grid_residual_cvec          the grid object                 colour-partitioned cvec
+   MG_LV_GRID_SLAB  pmg_dist_sample_cvec (built on a       pmg_grid_residual_cvec          the level (Lv->lrc): the cycle  cvec of the slab
+                    pmg_dist, any rank count)                                              brackets the slab sweeps
+   MG_LV_ST27       class-stencil sweeps (one device or    pmgk_st27_residual[_pair]       the level (Lv->lrc)             plane-padded natural order
+                    z-slab: `distributed`)
+   MG_LV_SELL       pmg_mcsor_sample_layout, or block      pmg_mcsor_residual_layout       the pmg_mcsor object            sliced-ELL layout
+                    sweeps where Lv->bg
+   MG_LV_ROWBLOCK   pmg_distmcsor_sample_layout            pmg_distmcsor_residual_layout   the pmg_distmcsor object        sliced-ELL layout, ghost rows last */
+typedef enum { MG_LV_EXACT, MG_LV_GRID, MG_LV_GRID_SLAB, MG_LV_ST27, MG_LV_SELL, MG_LV_ROWBLOCK } mg_kind;
+/* transfers between level l and l - 1, held by level l: none (level 0) | matrix-free Q1 from a grid level (cpos_dev: the coarse
+   level is permuted, else padded natural) | matrix-free Q1 between two levels in padded natural order | CSR products in layout numbering */
+typedef enum { MG_TR_NONE, MG_TR_Q1_GRID, MG_TR_Q1_NAT, MG_TR_CSR } mg_transfer;
+
 typedef struct {
+  mg_kind     kind;     /* assigned by the set-up bodies, */
+  mg_transfer transfer; /* and by nothing after them */
   int32_t   nx, ny, nz, n; /* global extents */
   int32_t   kz0, nzl;      /* owned planes (0, nz on a single device and on replicated levels) */
   int       padded;        /* plane-padded natural layout (class-stencil levels, Cholesky level): element (i,j,k) at off + i + nx (j + ny (k - kz0)) */
   int64_t   off;           /* = nx*ny when padded */
   int       distributed;   /* z-slab level of a multi-device hierarchy */
-  int       is_grid;
   pmg_grid  g;
   pmg_mcsor mc;
   int64_t   ld;
@@ -37,40 +58,43 @@ typedef struct {
   double   *x2; /* second buffer of the out-of-place class-stencil sweep (single-device levels): x and x2 swap after every directional sweep */
   /* transfers to the next coarser level, in layout numbering on the device */
   int32_t  P_nrows, R_nrows;
-  int32_t *cpos_dev; /* grid level only: layout position of every point of the next coarser level */
+  int32_t *cpos_dev; /* MG_TR_Q1_GRID onto a permuted coarse level: layout position of every point of that level (NULL: padded natural) */
   /* class-stencil form of a structured Galerkin level (natural-order vectors) */
-  int       is_st27, nat_transfer; /* nat_transfer: this level and the next coarser one are both in padded natural order */
-  int       grid_transfer;         /* matrix-free Q1 transfers from this grid level (cpos_dev == NULL: padded natural coarse level) */
   pmgk_st27 st;
   double   *st_coef, *st_idiag, *st_sqrtd, *st_sqrtd_scaled;
-  pmg_lrc   lrc; /* MATLRC update of a class-stencil level (grid / sliced-ELL levels keep theirs inside g / mc) */
+  pmg_lrc   lrc; /* MATLRC update of a class-stencil or slab grid level (mg_level_cycle_lrc); the other kinds keep theirs inside g / mc / dm */
   int32_t *P_rowpos, *P_rowptr, *P_col, *R_rowpos, *R_rowptr, *R_col;
   double  *P_val, *R_val;
   /* optional host copies (natural numbering) for inspection */
   hcsr A_host, P_host;
-  /* caller-supplied hierarchy (borrowed host CSR until set-up) */
-  hcsr A_user, P_user;
-  int32_t *A_rp_own, *A_ci_own, *P_rp_own, *P_ci_own; /* 32-bit copies of 64-bit PetscInt arrays, freed after set-up */
-  /* ROW BLOCK of a distributed hierarchy (pmg_mgmc_set_level_rowblock): A_user is this rank's rows in LOCAL numbering --
-     owned rows first, then one identity row per ghost (every row of another rank that this rank's operator, restriction
-     or the finer level's interpolation reads); the plan lists are host copies until set-up builds `dm` from them */
-  int           rb;
-  int32_t       rb_nowned, rb_ncolors;
-  int64_t       rb_row0;
-  int32_t      *rb_colors, *rb_send_idx, *rb_recv_src, *rb_recv_idx;
-  int64_t      *rb_send_ptr, *rb_recv_ptr, *rb_counts;
-  hcsr          R_user; /* rows of the restriction INTO the next coarser level that this rank owns there (borrowed) */
+  int32_t       rb_nowned; /* row block: the owned rows, first among the n local rows */
   pmg_distmcsor dm;
   int64_t       A_nnz, P_nnz; /* stored entries of a sliced-ELL level's operator / of its CSR interpolation (traffic accounting) */
-  /* block smoothing (pmg_mgmc_set_level_blocks): copies of the caller's blocks; set-up builds `bg` from them on the level's operator,
-     in the layout of `mc`, and the level's smoothing legs then run block sweeps */
-  int32_t        bg_nblocks, bg_ncolors, *bg_blockptr, *bg_blockrows, *bg_colors;
-  pmg_blockgibbs bg;
+  pmg_blockgibbs bg; /* block smoothing of an MG_LV_SELL level (pmg_mgmc_set_level_blocks): on the level's operator, in the layout of `mc` */
 } mg_level;
 
+/* What the caller hands in for one level before set-up.  The setters write it, the set-up bodies read it, and
+   pmg_mgmc_i_free_inputs empties it when a set-up has succeeded: nothing after set-up reads it. */
+typedef struct {
+  hcsr     A_user, P_user; /* caller-supplied hierarchy: borrowed host CSR */
+  hcsr     R_user;         /* row block: rows of the restriction INTO the next coarser level that this rank owns there (borrowed) */
+  int32_t *A_rp_own, *A_ci_own, *P_rp_own, *P_ci_own; /* 32-bit copies of 64-bit PetscInt arrays (owned) */
+  /* ROW BLOCK of a distributed hierarchy (pmg_mgmc_set_level_rowblock sets rb): A_user is this rank's rows in
+     LOCAL numbering -- owned rows first, then one identity row per ghost (every row of another rank that this rank's operator,
+     restriction or the finer level's interpolation reads); copies of the plan lists, from which set-up builds `dm` */
+  int      rb;
+  int32_t  rb_nowned, rb_ncolors;
+  int64_t  rb_row0;
+  int32_t *rb_colors, *rb_send_idx, *rb_recv_src, *rb_recv_idx;
+  int64_t *rb_send_ptr, *rb_recv_ptr, *rb_counts;
+  /* block smoothing (pmg_mgmc_set_level_blocks): copies of the caller's blocks, from which set-up builds `bg` */
+  int32_t  bg_nblocks, bg_ncolors, *bg_blockptr, *bg_blockrows, *bg_colors;
+} mg_level_in;
+
 struct pmg_mgmc_s {
-  int       nlevels;
-  mg_level *lv; /* lv[0] = coarsest */
+  int          nlevels;
+  mg_level    *lv; /* lv[0] = coarsest */
+  mg_level_in *in; /* [nlevels] */
   double    kappa, omega;
   int       nu, scaled, sweep_type;
   int       coarse_type, coarse_its; /* 0 = cholsampler, 1 = Gibbs sweeps */
@@ -141,16 +165,61 @@ static inline int pmg_mgmc_i_level_sweeps(const struct pmg_mgmc_s *h, int l) { r
 static inline int pmg_mgmc_i_has_blocks(const struct pmg_mgmc_s *h)
 {
   for (int l = 0; l < h->nlevels; ++l)
-    if (h->lv[l].bg_blockptr) return 1;
+    if (h->is_setup ? h->lv[l].bg != NULL : h->in[l].bg_blockptr != NULL) return 1;
   return 0;
 }
 
-static inline double level_rows(const mg_level *Lv) { /* owned unknowns: a z-slab's planes, a row block's rows */ return Lv->is_grid || Lv->padded ? (double)Lv->nx * Lv->ny * Lv->nzl : (double)(Lv->rb ? Lv->rb_nowned : Lv->n); }
+/* owned unknowns: a z-slab's planes, a row block's rows */
+static inline double level_rows(const mg_level *Lv)
+{
+  switch (Lv->kind) {
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB:
+  case MG_LV_ST27: return (double)Lv->nx * Lv->ny * Lv->nzl;
+  case MG_LV_ROWBLOCK: return (double)Lv->rb_nowned;
+  case MG_LV_SELL:
+  case MG_LV_EXACT: break; /* (never distributed) */
+  }
+  return (double)Lv->n;
+}
 
 static inline pmgk_st27_dims level_dims(const mg_level *Lv) { return (pmgk_st27_dims){Lv->nx, Lv->ny, Lv->nzl, Lv->kz0, Lv->nz}; }
 
-/* the low-rank update a level's sampler applies (held by the level, or by the grid object of a single-device grid level) */
-static inline pmg_lrc mg_level_lrc(const mg_level *Lv) { return Lv->lrc ? Lv->lrc : (Lv->is_grid ? pmg_grid_lrc(Lv->g) : NULL); }
+/* the low-rank update the level's SAMPLER applies, NULL if none */
+static inline pmg_lrc mg_level_sampler_lrc(const struct pmg_mgmc_s *h, int l)
+{
+  const mg_level *Lv = &h->lv[l];
+  switch (Lv->kind) {
+  case MG_LV_GRID: return pmg_grid_lrc(Lv->g);
+  case MG_LV_GRID_SLAB:
+  case MG_LV_ST27: return Lv->lrc;
+  case MG_LV_SELL: return pmg_mcsor_lrc(Lv->mc);
+  case MG_LV_ROWBLOCK: /* the pmg_distmcsor object's, which hands none out */
+  case MG_LV_EXACT: break; /* the factor is that of the explicit sum */
+  }
+  return NULL;
+}
+
+/* mg_path.lrc and the level diagnostics: the sampler's update where it is open to the cycle -- which hands it the batched noise,
+   announces the residual and charges its passes -- and to pmg_mgmc_level_lowrank_*.  A sliced-ELL sampler applies its own inside
+   its pmg_mcsor calls */
+static inline pmg_lrc mg_level_path_lrc(const struct pmg_mgmc_s *h, int l) { return h->lv[l].kind == MG_LV_SELL ? NULL : mg_level_sampler_lrc(h, l); }
+
+/* the update whose noise bracket and residual term the CYCLE applies itself: the one the level holds.  The samplers of the other
+   kinds bracket their own sweeps, and their residual calls subtract the term */
+static inline pmg_lrc mg_level_cycle_lrc(const struct pmg_mgmc_s *h, int l)
+{
+  const mg_level *Lv = &h->lv[l];
+  switch (Lv->kind) {
+  case MG_LV_GRID_SLAB:
+  case MG_LV_ST27: return Lv->lrc;
+  case MG_LV_EXACT:
+  case MG_LV_GRID:
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK: break;
+  }
+  return NULL;
+}
 
 /* ---- pmg_hier_host.c: host memory only.  A function that fails leaves its output matrix partly allocated: it stays the
    caller's to release with pmg_hcsr_free, which accepts that state. */
@@ -171,11 +240,16 @@ PMG_HIDDEN void       pmg_hier_parity_colouring(int32_t nx, int32_t ny, int32_t 
 PMG_HIDDEN int        pmg_mgmc_i_st27_out_of_place(const mg_level *Lv); /* the level's own iterate is swept out of place, into Lv->x2 */
 PMG_HIDDEN int        pmg_mgmc_i_level_wants_x2(const mg_level *Lv);    /* the set-up gives the level a second iterate buffer */
 PMG_HIDDEN pmg_status pmg_mgmc_i_halo_level(pmg_mgmc h, mg_level *Lv, double *v, void *stream);
+/* one directional sweep of a class-stencil level.  noisy: the cycle's, on (rhs, the level's own iterate) with draw *ctr, which it
+   advances; out of place where the level has a second buffer (the two then swap).  Not noisy: in place on the caller's (rhs, y),
+   the level's iterate, buffers and counter untouched (seed and ctr are not read) */
+PMG_HIDDEN pmg_status pmg_mgmc_i_st27_dir_sweep(pmg_mgmc h, mg_level *Lv, int dir, int noisy, const double *rhs, double *y, uint64_t seed, uint64_t *ctr, void *stream);
 PMG_HIDDEN pmg_status pmg_mgmc_i_rb_fold_allgather(pmg_mgmc h, double *v, void *stream);
 PMG_HIDDEN pmg_status pmg_mgmc_i_level_residual(pmg_mgmc h, int l, const double *b, const double *x, double *r, void *stream);
 PMG_HIDDEN pmg_status pmg_mgmc_i_restrict(pmg_mgmc h, int l, double *r_fine, double *b_coarse, void *stream);
 PMG_HIDDEN pmg_status pmg_mgmc_i_prolong_add(pmg_mgmc h, int l, const double *e_coarse, double *x_fine, int only_color, void *stream);
-/* ---- pmg_mgmc_chains.c, pmg_mgmc_level.c */
+/* ---- pmg_mgmc_setup.c, pmg_mgmc_chains.c, pmg_mgmc_level.c */
+PMG_HIDDEN void       pmg_mgmc_i_free_inputs(pmg_mgmc h); /* releases what h->in owns and zeroes the rest */
 PMG_HIDDEN void       pmg_mgmc_i_free_chains(pmg_mgmc h);
 PMG_HIDDEN pmg_status pmg_mgmc_i_level_checked(pmg_mgmc h, int32_t level, int need_coarser, mg_level **Lv);
 

@@ -20,7 +20,7 @@ pmg_status pmg_mgmc_level_sweep(pmg_mgmc h, int32_t level, int backward, int noi
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
   PMG_CHECK(b_lvl && x_lvl, PMG_ERR_ARG_NULL, "null vector");
   if (Lv->bg) return pmg_blockgibbs_dir_sweep(Lv->bg, backward ? PMG_SOR_BACKWARD_SWEEP : PMG_SOR_FORWARD_SWEEP, noisy != 0, seed, counter, NULL, b_lvl, x_lvl, stream); /* the block sweep the cycle runs */
-  PMG_CHECK(Lv->is_st27, PMG_ERR_SUP, "level %d: only class-stencil levels (use pmg_grid_* / pmg_mcsor_* for the others)", level);
+  PMG_CHECK(Lv->kind == MG_LV_ST27, PMG_ERR_SUP, "level %d: only class-stencil levels (use pmg_grid_* / pmg_mcsor_* for the others)", level);
   pmgk_st27 S = Lv->st;
   S.sqrtdiag  = h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd;
   if (pmg_mgmc_i_st27_out_of_place(Lv)) { /* the production kernel: out of place into the level's second buffer, then copied back */
@@ -37,9 +37,15 @@ pmg_status pmg_mgmc_level_residual(pmg_mgmc h, int32_t level, const double *b_lv
   mg_level *Lv;
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
   PMG_CHECK(b_lvl && x_lvl && r_lvl, PMG_ERR_ARG_NULL, "null vector");
-  if (Lv->is_grid || Lv->is_st27) return pmg_mgmc_i_level_residual(h, level, b_lvl, x_lvl, r_lvl, stream);
-  PMG_CHECK(Lv->mc, PMG_ERR_SUP, "level %d has no residual kernel", level);
-  return pmg_mcsor_residual_layout(Lv->mc, b_lvl, x_lvl, r_lvl, stream); /* (of a row block: the local rows, no exchange) */
+  switch (Lv->kind) {
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB:
+  case MG_LV_ST27: return pmg_mgmc_i_level_residual(h, level, b_lvl, x_lvl, r_lvl, stream);
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK: return pmg_mcsor_residual_layout(Lv->mc, b_lvl, x_lvl, r_lvl, stream); /* (of a row block: the local rows, no exchange) */
+  case MG_LV_EXACT: break;
+  }
+  PMG_FAIL(PMG_ERR_SUP, "level %d has no residual kernel", level);
 }
 
 /* b_coarse (level-1) = P^T r_fine (level); x_fine (level) += P e_coarse (level-1), both colours */
@@ -58,7 +64,7 @@ pmg_status pmg_mgmc_level_residual_restrict(pmg_mgmc h, int32_t level, const dou
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 1, &Lv));
   PMG_CHECK(b_lvl && x_lvl && b_coarse, PMG_ERR_ARG_NULL, "null vector");
   int done = 0;
-  if (Lv->is_grid && Lv->grid_transfer && !Lv->distributed && !Lv->lrc && !Lv->cpos_dev && !pmg_grid_lrc(Lv->g)) {
+  if (Lv->kind == MG_LV_GRID && Lv->transfer == MG_TR_Q1_GRID && !Lv->cpos_dev && !mg_level_sampler_lrc(h, level)) { /* (level_checked: no z-slabs here) */
     const pmgk_st27_dims CD = level_dims(&h->lv[level - 1]);
     PMG_CALL(pmg_grid_residual_restrict(Lv->g, b_lvl, x_lvl, NULL, NULL, &CD, b_coarse, &done, stream));
   }
@@ -75,11 +81,11 @@ pmg_status pmg_mgmc_level_prolong_add(pmg_mgmc h, int32_t level, const double *e
 }
 
 /* the MATLRC update of a level (src/pc_gamgmc.c:157-196), single device: held by the grid object on the grid level, by the
-   level on class-stencil levels */
+   level on class-stencil levels; a sliced-ELL level's sampler keeps its own to itself (PMG_ERR_ARG_WRONGSTATE here) */
 static pmg_status level_lrc(pmg_mgmc h, int32_t level, int need_coarser, mg_level **Lv, pmg_lrc *l)
 {
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, need_coarser, Lv));
-  *l = mg_level_lrc(*Lv);
+  *l = mg_level_path_lrc(h, level);
   PMG_CHECK(*l, PMG_ERR_ARG_WRONGSTATE, "level %d carries no low-rank update", level);
   return PMG_SUCCESS;
 }
@@ -92,14 +98,12 @@ pmg_status pmg_mgmc_level_lowrank_factors(pmg_mgmc h, int32_t level, int32_t *k,
   return pmg_lrc_get_compact(l, k, ns, rows_host, B_host, Bb_fwd_host, Bb_bwd_host);
 }
 
-/* what the low-rank passes of a level run over, on every kind of level (a sliced-ELL level's sampler holds its update itself):
-   the rank, the number of rows (the support rows of the row-compact form, every row of the dense form: *dense = 1) */
+/* what the low-rank passes of a level run over, on every kind of level: the rank, the number of rows (the support rows of the row-compact form, every row of the dense form: *dense = 1) */
 pmg_status pmg_mgmc_level_lowrank_sizes(pmg_mgmc h, int32_t level, int32_t *k, int64_t *rows, int *dense)
 {
   mg_level *Lv;
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
-  pmg_lrc l = mg_level_lrc(Lv);
-  if (!l && Lv->mc) l = pmg_mcsor_lrc(Lv->mc);
+  pmg_lrc l = mg_level_sampler_lrc(h, level);
   PMG_CHECK(l, PMG_ERR_ARG_WRONGSTATE, "level %d carries no low-rank update", level);
   pmg_lrc_get_sizes(l, k, rows, dense);
   if (dense && *dense && rows) *rows = (int64_t)level_rows(Lv);

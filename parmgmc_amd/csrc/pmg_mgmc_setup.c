@@ -5,7 +5,9 @@
  *   setup_stencil_body   DMDA default: class-stencil tables from the proxy hierarchy, matrix-free Q1 transfers, z-slabs
  *   setup_galerkin_body  DMDA with the full Galerkin products on the host (keep_host, PMG_MG_FULL_GALERKIN / _NO_STENCIL /
  *                        _CSR_TRANSFERS, or a grid whose coarse operators are no class stencils)
- * The host sparse tools they call are in pmg_hier_host.c, the cycle that runs on the result in pmg_mgmc.c.
+ * Each body gives every level its kind and transfer kind (mg_kind, mg_transfer) where it builds the level; nothing assigns them
+ * afterwards.  The setters write the inputs h->in, the bodies read them, pmg_mgmc_i_free_inputs releases them after a successful
+ * set-up.  The host sparse tools they call are in pmg_hier_host.c, the cycle that runs on the result in pmg_mgmc.c.
  */
 #include "pmg_mgmc_internal.h"
 #include <math.h>
@@ -16,7 +18,10 @@ static pmg_status mgmc_alloc(int32_t levels, pmg_mgmc *out)
   pmg_mgmc h = (pmg_mgmc)calloc(1, sizeof *h);
   PMG_CHECK(h, PMG_ERR_MEM, "out of host memory");
   h->lv = (mg_level *)calloc((size_t)levels, sizeof(mg_level));
-  if (!h->lv) {
+  h->in = (mg_level_in *)calloc((size_t)levels, sizeof(mg_level_in));
+  if (!h->lv || !h->in) {
+    free(h->lv);
+    free(h->in);
     free(h);
     PMG_FAIL(PMG_ERR_MEM, "out of host memory");
   }
@@ -53,6 +58,7 @@ pmg_status pmg_mgmc_create_dmda(int32_t nx, int32_t ny, int32_t nz, double kappa
           if ((d[q] - 1) % 2 != 0 || d[q] < 3) {
             const int32_t bad = d[q];
             free(h->lv);
+            free(h->in);
             free(h);
             PMG_FAIL(PMG_ERR_ARG_SIZ, "level %d has %d points in direction %d: vertex-centred 2:1 coarsening needs (n-1) even and n >= 3 on every refined level (use 2^k+1 points)", l, bad, q);
           }
@@ -148,7 +154,7 @@ pmg_status pmg_mgmc_set_level_operator(pmg_mgmc h, int32_t level, int32_t n, con
   Lv->n        = n;
   Lv->nx       = n;
   Lv->ny = Lv->nz = 1;
-  hcsr_borrow(&Lv->A_user, n, n, rowptr, colidx, vals);
+  hcsr_borrow(&h->in[level].A_user, n, n, rowptr, colidx, vals);
   return PMG_SUCCESS;
 }
 
@@ -157,7 +163,7 @@ pmg_status pmg_mgmc_set_level_interpolation(pmg_mgmc h, int32_t level, int32_t n
   PMG_CHECK(h && rowptr && colidx && vals, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(h->user_hier && !h->is_setup, PMG_ERR_ARG_WRONGSTATE, "interpolations belong to pmg_mgmc_create_hierarchy, before set-up");
   PMG_CHECK(level >= 1 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d", level);
-  hcsr_borrow(&h->lv[level].P_user, nrows, ncols, rowptr, colidx, vals);
+  hcsr_borrow(&h->in[level].P_user, nrows, ncols, rowptr, colidx, vals);
   return PMG_SUCCESS;
 }
 
@@ -209,22 +215,22 @@ pmg_status pmg_mgmc_set_level_rowblock(pmg_mgmc h, int32_t level, int64_t row0, 
   PMG_CHECK(h->user_hier && !h->is_setup && h->rb_dist, PMG_ERR_ARG_WRONGSTATE, "call pmg_mgmc_set_rowblock_transport first, before set-up");
   PMG_CHECK(level >= 1 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d (the coarsest level is replicated)", level);
   PMG_CHECK(row0 >= 0 && nowned >= 0 && ncolors >= 1, PMG_ERR_ARG_OUTOFRANGE, "row0 %lld, %d owned rows, %d colours", (long long)row0, nowned, ncolors);
-  mg_level    *Lv = &h->lv[level];
+  mg_level_in *in  = &h->in[level];
   const size_t nc1 = (size_t)ncolors + 1, ns = (size_t)send_ptr[ncolors], nr = (size_t)recv_ptr[ncolors];
   PMG_CHECK((ns == 0 || send_idx) && (nr == 0 || (recv_src && recv_idx)), PMG_ERR_ARG_NULL, "null index list");
-  free(Lv->rb_colors), free(Lv->rb_send_ptr), free(Lv->rb_recv_ptr), free(Lv->rb_counts), free(Lv->rb_send_idx), free(Lv->rb_recv_src), free(Lv->rb_recv_idx);
-  Lv->rb_colors   = (int32_t *)dup_bytes(colors_owned, sizeof(int32_t) * (size_t)nowned);
-  Lv->rb_send_ptr = (int64_t *)dup_bytes(send_ptr, sizeof(int64_t) * nc1);
-  Lv->rb_recv_ptr = (int64_t *)dup_bytes(recv_ptr, sizeof(int64_t) * nc1);
-  Lv->rb_counts   = (int64_t *)dup_bytes(counts, sizeof(int64_t) * (size_t)ncolors * (size_t)h->nranks);
-  Lv->rb_send_idx = (int32_t *)dup_bytes(send_idx, sizeof(int32_t) * ns);
-  Lv->rb_recv_src = (int32_t *)dup_bytes(recv_src, sizeof(int32_t) * nr);
-  Lv->rb_recv_idx = (int32_t *)dup_bytes(recv_idx, sizeof(int32_t) * nr);
-  PMG_CHECK(Lv->rb_colors && Lv->rb_send_ptr && Lv->rb_recv_ptr && Lv->rb_counts && Lv->rb_send_idx && Lv->rb_recv_src && Lv->rb_recv_idx, PMG_ERR_MEM, "out of host memory");
-  Lv->rb         = 1;
-  Lv->rb_row0    = row0;
-  Lv->rb_nowned  = nowned;
-  Lv->rb_ncolors = ncolors;
+  free(in->rb_colors), free(in->rb_send_ptr), free(in->rb_recv_ptr), free(in->rb_counts), free(in->rb_send_idx), free(in->rb_recv_src), free(in->rb_recv_idx);
+  in->rb_colors   = (int32_t *)dup_bytes(colors_owned, sizeof(int32_t) * (size_t)nowned);
+  in->rb_send_ptr = (int64_t *)dup_bytes(send_ptr, sizeof(int64_t) * nc1);
+  in->rb_recv_ptr = (int64_t *)dup_bytes(recv_ptr, sizeof(int64_t) * nc1);
+  in->rb_counts   = (int64_t *)dup_bytes(counts, sizeof(int64_t) * (size_t)ncolors * (size_t)h->nranks);
+  in->rb_send_idx = (int32_t *)dup_bytes(send_idx, sizeof(int32_t) * ns);
+  in->rb_recv_src = (int32_t *)dup_bytes(recv_src, sizeof(int32_t) * nr);
+  in->rb_recv_idx = (int32_t *)dup_bytes(recv_idx, sizeof(int32_t) * nr);
+  PMG_CHECK(in->rb_colors && in->rb_send_ptr && in->rb_recv_ptr && in->rb_counts && in->rb_send_idx && in->rb_recv_src && in->rb_recv_idx, PMG_ERR_MEM, "out of host memory");
+  in->rb         = 1;
+  in->rb_row0    = row0;
+  in->rb_nowned  = nowned;
+  in->rb_ncolors = ncolors;
   return PMG_SUCCESS;
 }
 
@@ -238,17 +244,17 @@ pmg_status pmg_mgmc_set_level_blocks(pmg_mgmc h, int32_t level, int32_t nblocks,
   PMG_CHECK(!h->is_setup, PMG_ERR_ARG_WRONGSTATE, "set the blocks of a level before pmg_mgmc_setup");
   PMG_CHECK(level >= 0 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d", level);
   PMG_CHECK(nblocks >= 0 && (blockrows || blockptr[nblocks] == 0), PMG_ERR_ARG_OUTOFRANGE, "%d blocks", nblocks);
-  PMG_CHECK(!h->rb_dist && !h->lv[level].rb, PMG_ERR_SUP, "block smoothing of row-block distributed hierarchies is not supported");
+  PMG_CHECK(!h->rb_dist && !h->in[level].rb, PMG_ERR_SUP, "block smoothing of row-block distributed hierarchies is not supported");
   PMG_CHECK(h->omega == 1.0, PMG_ERR_SUP, "block smoothing with omega = %g: a block sweep has no relaxation parameter", h->omega);
   PMG_CHECK(!h->lrc_k, PMG_ERR_SUP, "block smoothing of a hierarchy with a low-rank update (pmg_mgmc_set_lowrank) is not supported");
-  mg_level *Lv = &h->lv[level];
-  free(Lv->bg_blockptr), free(Lv->bg_blockrows), free(Lv->bg_colors);
-  Lv->bg_blockptr  = (int32_t *)dup_bytes(blockptr, sizeof(int32_t) * ((size_t)nblocks + 1));
-  Lv->bg_blockrows = (int32_t *)dup_bytes(blockrows, sizeof(int32_t) * (size_t)(blockptr[nblocks] > 0 ? blockptr[nblocks] : 0));
-  Lv->bg_colors    = block_colors ? (int32_t *)dup_bytes(block_colors, sizeof(int32_t) * (size_t)nblocks) : NULL;
-  PMG_CHECK(Lv->bg_blockptr && Lv->bg_blockrows && (Lv->bg_colors || !block_colors), PMG_ERR_MEM, "out of host memory");
-  Lv->bg_nblocks = nblocks;
-  Lv->bg_ncolors = ncolors;
+  mg_level_in *in = &h->in[level];
+  free(in->bg_blockptr), free(in->bg_blockrows), free(in->bg_colors);
+  in->bg_blockptr  = (int32_t *)dup_bytes(blockptr, sizeof(int32_t) * ((size_t)nblocks + 1));
+  in->bg_blockrows = (int32_t *)dup_bytes(blockrows, sizeof(int32_t) * (size_t)(blockptr[nblocks] > 0 ? blockptr[nblocks] : 0));
+  in->bg_colors    = block_colors ? (int32_t *)dup_bytes(block_colors, sizeof(int32_t) * (size_t)nblocks) : NULL;
+  PMG_CHECK(in->bg_blockptr && in->bg_blockrows && (in->bg_colors || !block_colors), PMG_ERR_MEM, "out of host memory");
+  in->bg_nblocks = nblocks;
+  in->bg_ncolors = ncolors;
   return PMG_SUCCESS;
 }
 
@@ -257,7 +263,7 @@ pmg_status pmg_mgmc_set_level_restriction(pmg_mgmc h, int32_t level, int32_t nro
   PMG_CHECK(h && rowptr && colidx && vals, PMG_ERR_ARG_NULL, "null argument");
   PMG_CHECK(h->user_hier && !h->is_setup, PMG_ERR_ARG_WRONGSTATE, "restrictions belong to pmg_mgmc_create_hierarchy, before set-up");
   PMG_CHECK(level >= 1 && level < h->nlevels, PMG_ERR_ARG_OUTOFRANGE, "level %d", level);
-  hcsr_borrow(&h->lv[level].R_user, nrows, ncols, rowptr, colidx, vals);
+  hcsr_borrow(&h->in[level].R_user, nrows, ncols, rowptr, colidx, vals);
   return PMG_SUCCESS;
 }
 
@@ -279,8 +285,7 @@ pmg_status pmg_mgmc_set_level_operator_idx(pmg_mgmc h, int32_t level, int64_t n,
   const int32_t *rp, *ci;
   int32_t       *rpo, *cio;
   PMG_CALL(pmg_narrow_csr(n, n, rowptr, colidx, idx_width, &rp, &ci, &rpo, &cio));
-  mg_level *Lv = &h->lv[level];
-  return adopt_narrowed(pmg_mgmc_set_level_operator(h, level, (int32_t)n, rp, ci, vals), &Lv->A_rp_own, &Lv->A_ci_own, rpo, cio);
+  return adopt_narrowed(pmg_mgmc_set_level_operator(h, level, (int32_t)n, rp, ci, vals), &h->in[level].A_rp_own, &h->in[level].A_ci_own, rpo, cio);
 }
 
 pmg_status pmg_mgmc_set_level_interpolation_idx(pmg_mgmc h, int32_t level, int64_t nrows, int64_t ncols, const void *rowptr, const void *colidx, const double *vals, int idx_width)
@@ -290,8 +295,7 @@ pmg_status pmg_mgmc_set_level_interpolation_idx(pmg_mgmc h, int32_t level, int64
   const int32_t *rp, *ci;
   int32_t       *rpo, *cio;
   PMG_CALL(pmg_narrow_csr(nrows, ncols, rowptr, colidx, idx_width, &rp, &ci, &rpo, &cio));
-  mg_level *Lv = &h->lv[level];
-  return adopt_narrowed(pmg_mgmc_set_level_interpolation(h, level, (int32_t)nrows, (int32_t)ncols, rp, ci, vals), &Lv->P_rp_own, &Lv->P_ci_own, rpo, cio);
+  return adopt_narrowed(pmg_mgmc_set_level_interpolation(h, level, (int32_t)nrows, (int32_t)ncols, rp, ci, vals), &h->in[level].P_rp_own, &h->in[level].P_ci_own, rpo, cio);
 }
 
 pmg_status pmg_mgmc_set_smoother(pmg_mgmc h, int scaled, double omega, int sweep_type, int32_t its)
@@ -422,7 +426,14 @@ pmg_status pmg_mgmc_get_level_layout(pmg_mgmc h, int32_t level, int32_t *kind, i
 {
   mg_level *Lv;
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
-  if (kind) *kind = Lv->is_grid ? 0 : (Lv->is_st27 ? 1 : (Lv->mc ? 2 : 3));
+  if (kind) switch (Lv->kind) {
+    case MG_LV_GRID:
+    case MG_LV_GRID_SLAB: *kind = 0; break;
+    case MG_LV_ST27: *kind = 1; break;
+    case MG_LV_SELL:
+    case MG_LV_ROWBLOCK: *kind = 2; break;
+    case MG_LV_EXACT: *kind = 3; break;
+    }
   if (ld) *ld = Lv->ld;
   if (off) *off = Lv->padded ? Lv->off : 0;
   return PMG_SUCCESS;
@@ -433,7 +444,7 @@ pmg_status pmg_mgmc_get_level_stencil(pmg_mgmc h, int32_t level, double *coef_ho
 {
   mg_level *Lv;
   PMG_CALL(pmg_mgmc_i_level_checked(h, level, 0, &Lv));
-  PMG_CHECK(Lv->is_st27, PMG_ERR_ARG_WRONGSTATE, "level %d is not a class-stencil level", level);
+  PMG_CHECK(Lv->kind == MG_LV_ST27, PMG_ERR_ARG_WRONGSTATE, "level %d is not a class-stencil level", level);
   if (coef_host) PMG_HIP(hipMemcpy(coef_host, Lv->st_coef, sizeof(double) * 27 * 27, hipMemcpyDeviceToHost));
   if (sqrtdiag_host) PMG_HIP(hipMemcpy(sqrtdiag_host, h->scaled ? Lv->st_sqrtd_scaled : Lv->st_sqrtd, sizeof(double) * 27, hipMemcpyDeviceToHost));
   return PMG_SUCCESS;
@@ -471,39 +482,30 @@ static pmg_status st27_install(mg_level *Lv, const double *coef, const int *have
   Lv->st.nzg   = Lv->nz;
   Lv->st.coef  = Lv->st_coef;
   Lv->st.idiag = Lv->st_idiag;
-  Lv->is_st27  = 1;
+  Lv->kind     = MG_LV_ST27;
   return PMG_SUCCESS;
 }
 
-/* Try to express the CSR operator of a structured level as 27 position-class stencils: *is_st27 = 1 and the level is
-   installed if every row equals its class stencil bit for bit (always the case for Galerkin operators of the
-   constant-coefficient fine operator), 0 otherwise (the caller keeps the sliced-ELL form). */
-static pmg_status st27_from_csr(mg_level *Lv, const hcsr *A, double omega, int *is_st27)
+/* Try to express the CSR operator of a structured level as 27 position-class stencils: the level is installed as an
+   MG_LV_ST27 level if every row equals its class stencil bit for bit (always the case for Galerkin operators of the
+   constant-coefficient fine operator); otherwise it is left as it was (the caller keeps the sliced-ELL form). */
+static pmg_status st27_from_csr(mg_level *Lv, const hcsr *A, double omega)
 {
   double coef[27 * 27];
   int    have[27];
-  *is_st27 = pmg_hier_st27_extract(Lv->nx, Lv->ny, Lv->nz, A, coef, have);
-  return *is_st27 ? st27_install(Lv, coef, have, omega) : PMG_SUCCESS;
+  return pmg_hier_st27_extract(Lv->nx, Lv->ny, Lv->nz, A, coef, have) ? st27_install(Lv, coef, have, omega) : PMG_SUCCESS;
 }
 
+/* deterministic sweep of a class-stencil level as a pmg_det_sweep_fn: the cycle's own sweep without its noise */
 typedef struct {
   pmg_mgmc  h;
   mg_level *Lv;
-} st27_det_ctx;
+} level_ref;
 
 static pmg_status st27_det_sweep(void *ctx, int dir, const double *b, double *y, void *stream)
 {
-  st27_det_ctx *c = (st27_det_ctx *)ctx;
-  const int     backward = dir == PMG_SOR_BACKWARD_SWEEP;
-  if (c->Lv->distributed) { /* z-slab: the two z-parity phases with a halo of the boundary planes after each */
-    PMG_KERNEL(pmgk_st27_sweep_phase(&c->Lv->st, backward, 0, c->h->omega, 0, 0, 0, b, y, stream));
-    PMG_CALL(pmg_mgmc_i_halo_level(c->h, c->Lv, y, stream));
-    PMG_KERNEL(pmgk_st27_sweep_phase(&c->Lv->st, backward, 1, c->h->omega, 0, 0, 0, b, y, stream));
-    PMG_CALL(pmg_mgmc_i_halo_level(c->h, c->Lv, y, stream));
-    return PMG_SUCCESS;
-  }
-  PMG_KERNEL(pmgk_st27_sweep(&c->Lv->st, backward, c->h->omega, 0, 0, 0, b, y, stream));
-  return PMG_SUCCESS;
+  const level_ref *c = (const level_ref *)ctx;
+  return pmg_mgmc_i_st27_dir_sweep(c->h, c->Lv, dir, 0, b, y, 0, NULL, stream);
 }
 
 /* deterministic sweep of the fine level of a z-slab hierarchy; sum of k-vectors over the ranks */
@@ -520,18 +522,23 @@ static pmg_status mg_reduce(void *ctx, double *vals_dev, int count, void *stream
    level's n x k block in natural numbering */
 static pmg_status level_attach_lrc(pmg_mgmc h, mg_level *Lv, const double *B_nat)
 {
-  if (Lv->is_grid) return pmg_grid_set_lowrank(Lv->g, h->lrc_k, B_nat, h->lrc_S);
-  if (Lv->mc) return pmg_mcsor_set_lowrank(Lv->mc, h->lrc_k, B_nat, h->lrc_S);
-  if (Lv->is_st27) {
+  switch (Lv->kind) {
+  case MG_LV_GRID:
+  case MG_LV_GRID_SLAB: return pmg_grid_set_lowrank(Lv->g, h->lrc_k, B_nat, h->lrc_S); /* (a slab hierarchy attaches on the device: stencil_attach_lowrank) */
+  case MG_LV_SELL:
+  case MG_LV_ROWBLOCK: return pmg_mcsor_set_lowrank(Lv->mc, h->lrc_k, B_nat, h->lrc_S); /* (a row block attaches to its pmg_distmcsor on the device) */
+  case MG_LV_ST27: {
     int64_t *pos = (int64_t *)malloc(sizeof(int64_t) * (size_t)Lv->n);
     PMG_CHECK(pos, PMG_ERR_MEM, "out of host memory");
     for (int32_t q = 0; q < Lv->n; ++q) pos[q] = q + Lv->off;
-    st27_det_ctx ctx = {h, Lv};
-    pmg_status   st  = pmg_lrc_build(&Lv->lrc, h->lrc_k, Lv->ld, Lv->n, B_nat, pos, h->lrc_S, st27_det_sweep, &ctx);
+    level_ref  ref = {h, Lv};
+    pmg_status st  = pmg_lrc_build(&Lv->lrc, h->lrc_k, Lv->ld, Lv->n, B_nat, pos, h->lrc_S, st27_det_sweep, &ref);
     free(pos);
     return st;
   }
-  return PMG_SUCCESS; /* coarsest level with the Cholesky sampler: the update goes into the factored matrix */
+  case MG_LV_EXACT: break; /* the update goes into the factored matrix */
+  }
+  return PMG_SUCCESS;
 }
 
 static pmg_status upload_transfer(const hcsr *M, const int32_t *rowpos_of, const int32_t *colpos_of, int32_t **rowpos, int32_t **rowptr, int32_t **col, double **val)
@@ -615,13 +622,15 @@ static pmg_status setup_restrict_attach_B(pmg_mgmc h, setup_scratch *s, const mg
 
 /* sliced-ELL level sampler from a host CSR in natural numbering, coloured by `rule` (PMG_COLORING_USER: by `colors`); a
    row block keys its noise on the global row.  Fills ld, A_nnz and pos (natural row -> layout position). */
-static pmg_status level_make_sell(pmg_mgmc h, mg_level *Lv, const hcsr *A, int rule, const int32_t *colors, int32_t *pos)
+static pmg_status level_make_sell(pmg_mgmc h, int l, const hcsr *A, int rule, const int32_t *colors, int32_t *pos)
 {
+  mg_level          *Lv = &h->lv[l];
+  const mg_level_in *in = &h->in[l];
   PMG_CALL(pmg_mcsor_create_csr(Lv->n, A->rp, A->ci, A->v, &Lv->mc));
   PMG_CALL(pmg_mcsor_set_natural_order(Lv->mc, 1));
   Lv->A_nnz = A->rp[Lv->n];
   PMG_CALL(pmg_mcsor_set_coloring(Lv->mc, rule, colors));
-  if (Lv->rb) PMG_CALL(pmg_mcsor_set_noise_row_offset(Lv->mc, Lv->rb_row0));
+  if (in->rb) PMG_CALL(pmg_mcsor_set_noise_row_offset(Lv->mc, in->rb_row0));
   PMG_CALL(pmg_mcsor_set_omega(Lv->mc, h->omega));
   PMG_CALL(pmg_mcsor_set_sweep_type(Lv->mc, h->sweep_type));
   PMG_CALL(pmg_mcsor_setup(Lv->mc));
@@ -629,11 +638,11 @@ static pmg_status level_make_sell(pmg_mgmc h, mg_level *Lv, const hcsr *A, int r
   PMG_CALL(pmg_mcsor_layout_len(Lv->mc, &ld32));
   Lv->ld = ld32;
   PMG_CALL(pmg_mcsor_get_layout(Lv->mc, pos));
-  if (!Lv->bg_blockptr) return PMG_SUCCESS;
+  if (!in->bg_blockptr) return PMG_SUCCESS;
   /* block smoothing: the same operator, vectors in the layout just built */
-  PMG_CHECK(h->omega == 1.0 && !h->lrc_k && !Lv->rb, PMG_ERR_SUP, "level with block smoothing: omega = 1, no low-rank update and no row block");
-  PMG_CALL(pmg_blockgibbs_create_csr(Lv->n, A->rp, A->ci, A->v, Lv->bg_nblocks, Lv->bg_blockptr, Lv->bg_blockrows, &Lv->bg));
-  if (Lv->bg_colors) PMG_CALL(pmg_blockgibbs_set_coloring(Lv->bg, Lv->bg_ncolors, Lv->bg_colors));
+  PMG_CHECK(h->omega == 1.0 && !h->lrc_k && !in->rb, PMG_ERR_SUP, "level with block smoothing: omega = 1, no low-rank update and no row block");
+  PMG_CALL(pmg_blockgibbs_create_csr(Lv->n, A->rp, A->ci, A->v, in->bg_nblocks, in->bg_blockptr, in->bg_blockrows, &Lv->bg));
+  if (in->bg_colors) PMG_CALL(pmg_blockgibbs_set_coloring(Lv->bg, in->bg_ncolors, in->bg_colors));
   PMG_CALL(pmg_blockgibbs_set_layout(Lv->bg, ld32, pos));
   return pmg_blockgibbs_setup(Lv->bg);
 }
@@ -661,25 +670,26 @@ static pmg_status alloc_level_vectors(pmg_mgmc h)
 static pmg_status user_level_check(pmg_mgmc h, int l)
 {
   const int top = h->nlevels - 1;
-  mg_level *Lv  = &h->lv[l];
-  PMG_CHECK(Lv->A_user.rp, PMG_ERR_ARG_WRONGSTATE, "level %d has no operator", l);
-  PMG_CHECK(!Lv->bg_blockptr || l >= 1 || h->coarse_type == 1, PMG_ERR_ARG_WRONG, "level 0 has blocks but is sampled exactly: block smoothing applies to a Gibbs coarse level (pmg_mgmc_set_coarse)");
+  const mg_level    *Lv = &h->lv[l];
+  const mg_level_in *in = &h->in[l];
+  PMG_CHECK(in->A_user.rp, PMG_ERR_ARG_WRONGSTATE, "level %d has no operator", l);
+  PMG_CHECK(!in->bg_blockptr || l >= 1 || h->coarse_type == 1, PMG_ERR_ARG_WRONG, "level 0 has blocks but is sampled exactly: block smoothing applies to a Gibbs coarse level (pmg_mgmc_set_coarse)");
   if (h->rb_dist) { /* row blocks from level rb_fold upwards; the levels below are replicated (the coarsest sampled exactly) */
     if (l == 0) {
       h->rb_fold = 1;
-      while (h->rb_fold <= top && !h->lv[h->rb_fold].rb) ++h->rb_fold;
+      while (h->rb_fold <= top && !h->in[h->rb_fold].rb) ++h->rb_fold;
       PMG_CHECK(h->rb_fold <= top, PMG_ERR_ARG_WRONGSTATE, "row-block hierarchy without a row-block level (pmg_mgmc_set_level_rowblock)");
       PMG_CHECK(h->rb_c0_starts[h->nranks] == h->lv[h->rb_fold - 1].n, PMG_ERR_ARG_SIZ, "the row blocks of the highest replicated level cover %lld rows, level %d has %d", (long long)h->rb_c0_starts[h->nranks], h->rb_fold - 1, h->lv[h->rb_fold - 1].n);
     }
-    PMG_CHECK(l < h->rb_fold ? !Lv->rb : Lv->rb, PMG_ERR_ARG_WRONGSTATE, "row-block hierarchy: level %d %s", l, l < h->rb_fold ? "lies below a replicated level and must be replicated too" : "has no row block (pmg_mgmc_set_level_rowblock)");
+    PMG_CHECK(l < h->rb_fold ? !in->rb : in->rb, PMG_ERR_ARG_WRONGSTATE, "row-block hierarchy: level %d %s", l, l < h->rb_fold ? "lies below a replicated level and must be replicated too" : "has no row block (pmg_mgmc_set_level_rowblock)");
     PMG_CHECK(h->coarse_type == 0, PMG_ERR_SUP, "row-block hierarchies: exact coarse sampler");
     if (l >= h->rb_fold) {
-      PMG_CHECK(Lv->P_user.rp && Lv->R_user.rp && Lv->P_user.nr == Lv->rb_nowned && Lv->P_user.nc == h->lv[l - 1].n && Lv->R_user.nc == Lv->n, PMG_ERR_ARG_SIZ, "level %d: interpolation rows = owned rows, its columns and the restriction's in local numbering", l);
-      PMG_CHECK(Lv->R_user.nr == (l == h->rb_fold ? (int32_t)(h->rb_c0_starts[h->rank + 1] - h->rb_c0_starts[h->rank]) : h->lv[l - 1].rb_nowned), PMG_ERR_ARG_SIZ, "level %d: the restriction has one row per owned row of level %d", l, l - 1);
+      PMG_CHECK(in->P_user.rp && in->R_user.rp && in->P_user.nr == in->rb_nowned && in->P_user.nc == h->lv[l - 1].n && in->R_user.nc == Lv->n, PMG_ERR_ARG_SIZ, "level %d: interpolation rows = owned rows, its columns and the restriction's in local numbering", l);
+      PMG_CHECK(in->R_user.nr == (l == h->rb_fold ? (int32_t)(h->rb_c0_starts[h->rank + 1] - h->rb_c0_starts[h->rank]) : h->in[l - 1].rb_nowned), PMG_ERR_ARG_SIZ, "level %d: the restriction has one row per owned row of level %d", l, l - 1);
       return PMG_SUCCESS;
     }
   }
-  PMG_CHECK(l == 0 || (Lv->P_user.rp && Lv->P_user.nr == Lv->n && Lv->P_user.nc == h->lv[l - 1].n), PMG_ERR_ARG_SIZ, "interpolation of %slevel %d missing or of the wrong shape", h->rb_dist ? "the replicated " : "", l);
+  PMG_CHECK(l == 0 || (in->P_user.rp && in->P_user.nr == Lv->n && in->P_user.nc == h->lv[l - 1].n), PMG_ERR_ARG_SIZ, "interpolation of %slevel %d missing or of the wrong shape", h->rb_dist ? "the replicated " : "", l);
   return PMG_SUCCESS;
 }
 
@@ -687,26 +697,28 @@ static pmg_status user_level_check(pmg_mgmc h, int l)
    that is never swept; then the ghost-update plan in layout positions */
 static pmg_status user_level_rowblock(pmg_mgmc h, int l, setup_scratch *s)
 {
-  mg_level *Lv = &h->lv[l];
-  PMG_CHECK(Lv->rb_nowned <= Lv->n, PMG_ERR_ARG_SIZ, "level %d: %d owned rows of %d local rows", l, Lv->rb_nowned, Lv->n);
+  mg_level          *Lv = &h->lv[l];
+  const mg_level_in *in = &h->in[l];
+  PMG_CHECK(in->rb_nowned <= Lv->n, PMG_ERR_ARG_SIZ, "level %d: %d owned rows of %d local rows", l, in->rb_nowned, Lv->n);
   int32_t *col = (int32_t *)setup_tmp(s, sizeof(int32_t) * (size_t)Lv->n);
   PMG_CHECK(col, PMG_ERR_MEM, "out of host memory");
-  for (int32_t r = 0; r < Lv->n; ++r) col[r] = r < Lv->rb_nowned ? Lv->rb_colors[r] : Lv->rb_ncolors;
-  PMG_CALL(level_make_sell(h, Lv, &Lv->A_user, PMG_COLORING_USER, col, s->pos[l]));
-  const int64_t  ns = Lv->rb_send_ptr[Lv->rb_ncolors], nr = Lv->rb_recv_ptr[Lv->rb_ncolors];
+  for (int32_t r = 0; r < Lv->n; ++r) col[r] = r < in->rb_nowned ? in->rb_colors[r] : in->rb_ncolors;
+  Lv->rb_nowned = in->rb_nowned;
+  PMG_CALL(level_make_sell(h, l, &in->A_user, PMG_COLORING_USER, col, s->pos[l]));
+  const int64_t  ns = in->rb_send_ptr[in->rb_ncolors], nr = in->rb_recv_ptr[in->rb_ncolors];
   const int32_t *pos = s->pos[l];
   int32_t       *sp = (int32_t *)setup_tmp(s, sizeof(int32_t) * (size_t)(ns + nr + 2));
   PMG_CHECK(sp, PMG_ERR_MEM, "out of host memory");
   int32_t *rp = sp + ns + 1;
   for (int64_t q = 0; q < ns; ++q) {
-    PMG_CHECK(Lv->rb_send_idx[q] >= 0 && Lv->rb_send_idx[q] < Lv->rb_nowned, PMG_ERR_ARG_OUTOFRANGE, "level %d: send row %d is not an owned row", l, Lv->rb_send_idx[q]);
-    sp[q] = pos[Lv->rb_send_idx[q]];
+    PMG_CHECK(in->rb_send_idx[q] >= 0 && in->rb_send_idx[q] < in->rb_nowned, PMG_ERR_ARG_OUTOFRANGE, "level %d: send row %d is not an owned row", l, in->rb_send_idx[q]);
+    sp[q] = pos[in->rb_send_idx[q]];
   }
   for (int64_t q = 0; q < nr; ++q) {
-    PMG_CHECK(Lv->rb_recv_idx[q] >= Lv->rb_nowned && Lv->rb_recv_idx[q] < Lv->n, PMG_ERR_ARG_OUTOFRANGE, "level %d: receive row %d is not a ghost row", l, Lv->rb_recv_idx[q]);
-    rp[q] = pos[Lv->rb_recv_idx[q]];
+    PMG_CHECK(in->rb_recv_idx[q] >= in->rb_nowned && in->rb_recv_idx[q] < Lv->n, PMG_ERR_ARG_OUTOFRANGE, "level %d: receive row %d is not a ghost row", l, in->rb_recv_idx[q]);
+    rp[q] = pos[in->rb_recv_idx[q]];
   }
-  return pmg_distmcsor_create(Lv->mc, h->rb_dist, Lv->rb_ncolors, Lv->rb_send_ptr, sp, Lv->rb_counts, Lv->rb_recv_ptr, Lv->rb_recv_src, rp, &Lv->dm);
+  return pmg_distmcsor_create(Lv->mc, h->rb_dist, in->rb_ncolors, in->rb_send_ptr, sp, in->rb_counts, in->rb_recv_ptr, in->rb_recv_src, rp, &Lv->dm);
 }
 
 /* row blocks: B_{l-1} = P_l^T B_l column by column on the device, with the V-cycle's own restriction (s->Bdev: level l's
@@ -732,7 +744,7 @@ static pmg_status user_rowblock_restrict_B(pmg_mgmc h, int l, setup_scratch *s)
   PMG_HIP(hipMemcpy(Bl, s->Bdev, sizeof(double) * (size_t)Cc->ld * k, hipMemcpyDeviceToHost));
   for (int32_t c = 0; c < h->lrc_k; ++c)
     for (int32_t r = 0; r < Cc->n; ++r) B0[(size_t)Cc->n * c + r] = Bl[(size_t)Cc->ld * c + s->pos[l - 1][r]];
-  if (l - 1 == 0) return pmg_chol_create_csr_lowrank(Cc->n, Cc->A_user.rp, Cc->A_user.ci, Cc->A_user.v, h->lrc_k, s->Bcur, h->lrc_S, &h->chol);
+  if (l - 1 == 0) return pmg_chol_create_csr_lowrank(Cc->n, h->in[0].A_user.rp, h->in[0].A_user.ci, h->in[0].A_user.v, h->lrc_k, s->Bcur, h->lrc_S, &h->chol);
   return level_attach_lrc(h, Cc, s->Bcur);
 }
 
@@ -741,17 +753,25 @@ static pmg_status setup_user_body(pmg_mgmc h, setup_scratch *s)
   const int top = h->nlevels - 1;
   int32_t **pos = s->pos;
   for (int l = 0; l <= top; ++l) {
-    mg_level *Lv = &h->lv[l];
+    mg_level          *Lv = &h->lv[l];
+    const mg_level_in *in = &h->in[l];
     PMG_CALL(user_level_check(h, l));
     pos[l] = (int32_t *)malloc(sizeof(int32_t) * (size_t)Lv->n);
     PMG_CHECK(pos[l], PMG_ERR_MEM, "out of host memory");
-    if (Lv->rb) PMG_CALL(user_level_rowblock(h, l, s));
-    else if (l > 0 || h->coarse_type == 1) PMG_CALL(level_make_sell(h, Lv, &Lv->A_user, h->aij_coloring, NULL, pos[l])); /* PMG_COLORING_GREEDY unless pmg_mgmc_set_coloring said otherwise */
-    else {
+    Lv->kind     = in->rb ? MG_LV_ROWBLOCK : (l > 0 || h->coarse_type == 1 ? MG_LV_SELL : MG_LV_EXACT);
+    Lv->transfer = l > 0 ? MG_TR_CSR : MG_TR_NONE;
+    switch (Lv->kind) {
+    case MG_LV_ROWBLOCK: PMG_CALL(user_level_rowblock(h, l, s)); break;
+    case MG_LV_SELL: PMG_CALL(level_make_sell(h, l, &in->A_user, h->aij_coloring, NULL, pos[l])); break; /* PMG_COLORING_GREEDY unless pmg_mgmc_set_coloring said otherwise */
+    case MG_LV_EXACT:
       Lv->ld = Lv->n;
       for (int32_t q = 0; q < Lv->n; ++q) pos[l][q] = q;
+      if (!h->lrc_k) PMG_CALL(pmg_chol_create_csr(Lv->n, in->A_user.rp, in->A_user.ci, in->A_user.v, &h->chol));
+      break;
+    case MG_LV_GRID:
+    case MG_LV_GRID_SLAB:
+    case MG_LV_ST27: break; /* DMDA hierarchies only */
     }
-    if (l == 0 && h->coarse_type == 0 && !h->lrc_k) PMG_CALL(pmg_chol_create_csr(Lv->n, Lv->A_user.rp, Lv->A_user.ci, Lv->A_user.v, &h->chol));
   }
   s->Bcur = h->lrc_B; /* level-l block of the low-rank factor, natural numbering (owned by h at the top) */
   if (h->lrc_k && h->rb_dist) { /* row blocks: the block in the level's LAYOUT on the device, zero on the ghost rows */
@@ -764,20 +784,22 @@ static pmg_status setup_user_body(pmg_mgmc h, setup_scratch *s)
     PMG_CALL(pmg_distmcsor_set_lowrank_dev(T->dm, h->lrc_k, s->Bdev, h->lrc_S));
   } else if (h->lrc_k) PMG_CALL(level_attach_lrc(h, &h->lv[top], s->Bcur));
   for (int l = top; l >= 1; --l) {
-    mg_level *U = &h->lv[l], *Cc = &h->lv[l - 1];
-    if (!U->rb) PMG_CALL(pmg_hcsr_transpose(&U->P_user, &s->R));
-    if (h->lrc_k && !U->rb) { /* B_{l-1} = P_l^T B_l, src/pc_gamgmc.c:177-178 */
+    mg_level          *U = &h->lv[l], *Cc = &h->lv[l - 1];
+    const mg_level_in *in = &h->in[l], *cin = &h->in[l - 1];
+    const int          rb = U->kind == MG_LV_ROWBLOCK;
+    if (!rb) PMG_CALL(pmg_hcsr_transpose(&in->P_user, &s->R));
+    if (h->lrc_k && !rb) { /* B_{l-1} = P_l^T B_l, src/pc_gamgmc.c:177-178 */
       PMG_CALL(setup_restrict_attach_B(h, s, U, Cc));
-      if (l - 1 == 0 && h->coarse_type == 0) PMG_CALL(pmg_chol_create_csr_lowrank(Cc->n, Cc->A_user.rp, Cc->A_user.ci, Cc->A_user.v, h->lrc_k, s->Bcur, h->lrc_S, &h->chol));
+      if (Cc->kind == MG_LV_EXACT) PMG_CALL(pmg_chol_create_csr_lowrank(Cc->n, cin->A_user.rp, cin->A_user.ci, cin->A_user.v, h->lrc_k, s->Bcur, h->lrc_S, &h->chol));
     }
-    U->P_nrows = U->P_user.nr;
-    U->R_nrows = U->rb ? U->R_user.nr : s->R.nr;
-    PMG_CALL(upload_transfer(&U->P_user, pos[l], pos[l - 1], &U->P_rowpos, &U->P_rowptr, &U->P_col, &U->P_val));
-    U->P_nnz = U->P_user.rp[U->P_user.nr];
-    if (!U->rb) PMG_CALL(upload_transfer(&s->R, pos[l - 1], pos[l], &U->R_rowpos, &U->R_rowptr, &U->R_col, &U->R_val));
+    U->P_nrows = in->P_user.nr;
+    U->R_nrows = rb ? in->R_user.nr : s->R.nr;
+    PMG_CALL(upload_transfer(&in->P_user, pos[l], pos[l - 1], &U->P_rowpos, &U->P_rowptr, &U->P_col, &U->P_val));
+    U->P_nnz = in->P_user.rp[in->P_user.nr];
+    if (!rb) PMG_CALL(upload_transfer(&s->R, pos[l - 1], pos[l], &U->R_rowpos, &U->R_rowptr, &U->R_col, &U->R_val));
     else /* the caller's rows of P^T: owned rows of level l-1 (on the replicated coarsest level: this rank's block of the global rows) */
-      PMG_CALL(upload_transfer(&U->R_user, pos[l - 1] + (l == h->rb_fold ? h->rb_c0_starts[h->rank] : 0), pos[l], &U->R_rowpos, &U->R_rowptr, &U->R_col, &U->R_val));
-    if (U->rb && l == h->rb_fold && l - 1 >= 1) { /* the replicated level below keeps its vectors in a sliced-ELL layout: all-gather through natural order */
+      PMG_CALL(upload_transfer(&in->R_user, pos[l - 1] + (l == h->rb_fold ? h->rb_c0_starts[h->rank] : 0), pos[l], &U->R_rowpos, &U->R_rowptr, &U->R_col, &U->R_val));
+    if (rb && l == h->rb_fold && l - 1 >= 1) { /* the replicated level below keeps its vectors in a sliced-ELL layout: all-gather through natural order */
       int32_t *iota = (int32_t *)setup_tmp(s, sizeof(int32_t) * (size_t)Cc->n);
       PMG_CHECK(iota, PMG_ERR_MEM, "out of host memory");
       for (int32_t q = 0; q < Cc->n; ++q) iota[q] = q;
@@ -786,18 +808,7 @@ static pmg_status setup_user_body(pmg_mgmc h, setup_scratch *s)
       PMG_CALL(pmg_dev_alloc((void **)&h->rb_fold_buf, sizeof(double) * (size_t)Cc->n));
     }
     pmg_hcsr_free(&s->R);
-    if (h->lrc_k && U->rb) PMG_CALL(user_rowblock_restrict_B(h, l, s));
-  }
-  for (int l = 0; l <= top; ++l) {
-    mg_level *Lv = &h->lv[l];
-    memset(&Lv->A_user, 0, sizeof Lv->A_user); /* borrowed arrays are released */
-    memset(&Lv->P_user, 0, sizeof Lv->P_user);
-    memset(&Lv->R_user, 0, sizeof Lv->R_user);
-    free(Lv->A_rp_own);
-    free(Lv->A_ci_own);
-    free(Lv->P_rp_own);
-    free(Lv->P_ci_own);
-    Lv->A_rp_own = Lv->A_ci_own = Lv->P_rp_own = Lv->P_ci_own = NULL;
+    if (h->lrc_k && rb) PMG_CALL(user_rowblock_restrict_B(h, l, s));
   }
   PMG_CALL(alloc_level_vectors(h));
   h->n_io     = h->lv[top].n; /* the caller's vectors: one entry per (local) row of the finest level */
@@ -813,7 +824,7 @@ static pmg_status setup_galerkin_body(pmg_mgmc h, setup_scratch *s, int no_stenc
   int32_t **pos = s->pos; /* natural index -> layout position per level */
   /* finest level: matrix-free grid operator */
   mg_level *F = &h->lv[top];
-  F->is_grid  = 1;
+  F->kind     = MG_LV_GRID;
   PMG_CALL(pmg_grid_create(F->nx, F->ny, F->nz, 0, F->nz, h->kappa, &F->g));
   h->own_grid = 1;
   PMG_CALL(pmg_grid_set_omega(F->g, h->omega));
@@ -840,26 +851,27 @@ static pmg_status setup_galerkin_body(pmg_mgmc h, setup_scratch *s, int no_stenc
     /* coarse level operator object: a class-stencil level if the operator is one, else a sliced-ELL level under the parity
        colouring; the Cholesky level keeps padded natural order */
     const int is_coarsest = (l - 1 == 0), sampled = !is_coarsest || h->coarse_type == 1;
-    int       is_st27     = 0;
     pos[l - 1]            = (int32_t *)malloc(sizeof(int32_t) * (size_t)Cc->n);
     PMG_CHECK(pos[l - 1], PMG_ERR_MEM, "out of host memory");
-    if (sampled && !no_stencil) PMG_CALL(st27_from_csr(Cc, &s->Ac, h->omega, &is_st27));
-    if (is_st27 || !sampled) level_set_padded(Cc, pos[l - 1]);
+    Cc->kind = sampled ? MG_LV_SELL : MG_LV_EXACT;
+    if (sampled && !no_stencil) PMG_CALL(st27_from_csr(Cc, &s->Ac, h->omega)); /* an MG_LV_ST27 level where the operator allows */
+    if (Cc->kind != MG_LV_SELL) level_set_padded(Cc, pos[l - 1]);
     else {
       int32_t *col = (int32_t *)setup_tmp(s, sizeof(int32_t) * (size_t)Cc->n);
       PMG_CHECK(col, PMG_ERR_MEM, "out of host memory");
       pmg_hier_parity_colouring(Cc->nx, Cc->ny, Cc->nz, col);
-      PMG_CALL(level_make_sell(h, Cc, &s->Ac, PMG_COLORING_USER, col, pos[l - 1]));
+      PMG_CALL(level_make_sell(h, l - 1, &s->Ac, PMG_COLORING_USER, col, pos[l - 1]));
     }
     if (h->lrc_k) PMG_CALL(setup_restrict_attach_B(h, s, U, Cc));
     if (is_coarsest && h->coarse_type == 0) PMG_CALL(pmg_chol_create_csr_lowrank(Cc->n, s->Ac.rp, s->Ac.ci, s->Ac.v, h->lrc_k, s->Bcur, h->lrc_S, &h->chol));
     /* transfers: matrix-free Q1 kernels from the grid level and between natural-order levels, CSR products in
        layout numbering otherwise */
-    if (U->is_grid && !csr_transfers) {
-      U->grid_transfer = 1;
+    if (U->kind == MG_LV_GRID && !csr_transfers) {
+      U->transfer = MG_TR_Q1_GRID;
       if (!Cc->padded) PMG_CALL(pmg_dev_upload((void **)&U->cpos_dev, pos[l - 1], sizeof(int32_t) * (size_t)Cc->n));
-    } else if (U->is_st27 && Cc->padded && !csr_transfers) U->nat_transfer = 1;
+    } else if (U->kind == MG_LV_ST27 && Cc->padded && !csr_transfers) U->transfer = MG_TR_Q1_NAT;
     else {
+      U->transfer = MG_TR_CSR;
       U->P_nrows = s->P.nr;
       U->R_nrows = s->R.nr;
       PMG_CALL(upload_transfer(&s->P, pos[l], pos[l - 1], &U->P_rowpos, &U->P_rowptr, &U->P_col, &U->P_val));
@@ -907,9 +919,9 @@ static pmg_status stencil_attach_lowrank(pmg_mgmc h, setup_scratch *s)
     for (int c = 0; c < k; ++c) PMG_CALL(pmg_mgmc_i_restrict(h, l, s->Bdev + (size_t)Lv->ld * c, s->Bdev2 + (size_t)Cc->ld * c, NULL)); /* B_{l-1} = P_l^T B_l */
     PMG_HIP(hipDeviceSynchronize());
     setup_next_Bdev(s);
-    if (Cc->is_st27) { /* a sampled level (not the Cholesky level) */
-      st27_det_ctx ctx = {h, Cc};
-      PMG_CALL(pmg_lrc_build_dev(&Cc->lrc, k, Cc->ld, s->Bdev, h->lrc_S, st27_det_sweep, &ctx, Cc->distributed ? mg_reduce : NULL, h));
+    if (Cc->kind == MG_LV_ST27) { /* a sampled level (not the Cholesky level) */
+      level_ref ref = {h, Cc};
+      PMG_CALL(pmg_lrc_build_dev(&Cc->lrc, k, Cc->ld, s->Bdev, h->lrc_S, st27_det_sweep, &ref, Cc->distributed ? mg_reduce : NULL, h));
     }
   }
   /* coarsest block to the host, natural numbering (the padded layout minus its ghost planes) */
@@ -929,7 +941,7 @@ static pmg_status stencil_attach_lowrank(pmg_mgmc h, setup_scratch *s)
 static pmg_status slab_agree_fused_rr(pmg_mgmc h, int l)
 {
   mg_level *Lv = &h->lv[l];
-  if (!(l >= 1 && Lv->is_grid && Lv->distributed && Lv->grid_transfer && !Lv->cpos_dev && !h->no_fused && (!h->lrc_k || (Lv->lrc && h->lv[l - 1].lrc)) && pmg_switch(PMG_SW_GRID_FUSED_RR_SLAB))) return PMG_SUCCESS;
+  if (!(Lv->kind == MG_LV_GRID_SLAB && Lv->distributed && Lv->transfer == MG_TR_Q1_GRID && !Lv->cpos_dev && !h->no_fused && (!h->lrc_k || (mg_level_cycle_lrc(h, l) && mg_level_cycle_lrc(h, l - 1))) && pmg_switch(PMG_SW_GRID_FUSED_RR_SLAB))) return PMG_SUCCESS;
   const int32_t *fc = h->cuts + (size_t)l * (size_t)(h->nranks + 1), *cc = h->cuts + (size_t)(l - 1) * (size_t)(h->nranks + 1);
   int            ok = 1;
   for (int r = 0; r < h->nranks; ++r) ok = ok && fc[r + 1] - fc[r] >= 2 && cc[r + 1] - cc[r] >= 1;
@@ -964,7 +976,8 @@ static pmg_status setup_stencil_body(pmg_mgmc h, setup_scratch *s)
   const st27_table *tab = s->tab;
   const int top = h->nlevels - 1;
   mg_level *F   = &h->lv[top];
-  F->is_grid    = 1;
+  F->kind       = h->dist ? MG_LV_GRID_SLAB : MG_LV_GRID;
+  F->transfer   = MG_TR_Q1_GRID;
   if (!F->g) {
     PMG_CALL(pmg_grid_create(F->nx, F->ny, F->nz, 0, F->nz, h->kappa, &F->g));
     h->own_grid = 1;
@@ -972,7 +985,6 @@ static pmg_status setup_stencil_body(pmg_mgmc h, setup_scratch *s)
   PMG_CALL(pmg_grid_set_omega(F->g, h->omega));
   PMG_CALL(pmg_grid_set_sweep_type(F->g, h->sweep_type));
   PMG_CALL(pmg_grid_cvec_len(F->g, &F->ld));
-  F->grid_transfer = 1;
   if (h->dist) { /* which levels stay distributed */
     const int nr1 = h->nranks + 1;
     int64_t   cap = 0, rep = pmg_switch_wide(PMG_SW_MG_REPLICATE_BELOW); /* default 2^19 */
@@ -998,7 +1010,8 @@ static pmg_status setup_stencil_body(pmg_mgmc h, setup_scratch *s)
     mg_level *Lv = &h->lv[l];
     level_set_padded(Lv, NULL);
     if (l > 0 || h->coarse_type == 1) PMG_CALL(st27_install(Lv, tab[l].coef, tab[l].have, h->omega));
-    if (l > 0) Lv->nat_transfer = 1;
+    else Lv->kind = MG_LV_EXACT;
+    if (l > 0) Lv->transfer = MG_TR_Q1_NAT;
   }
   if (h->lrc_k) PMG_CALL(stencil_attach_lowrank(h, s)); /* leaves the coarsest block in s->Bcur */
   if (h->coarse_type == 0) {
@@ -1044,7 +1057,19 @@ pmg_status pmg_mgmc_setup(pmg_mgmc h)
   pmg_status st = s.pos ? PMG_SUCCESS : pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of host memory");
   if (!st) st = h->user_hier ? setup_user_body(h, &s) : setup_dmda_body(h, &s);
   setup_release(&s);
+  if (!st) pmg_mgmc_i_free_inputs(h); /* a failed set-up keeps them */
   return st;
+}
+
+void pmg_mgmc_i_free_inputs(pmg_mgmc h)
+{
+  for (int l = 0; l < h->nlevels && h->in; ++l) {
+    mg_level_in *in = &h->in[l];
+    free(in->A_rp_own), free(in->A_ci_own), free(in->P_rp_own), free(in->P_ci_own);
+    free(in->rb_colors), free(in->rb_send_ptr), free(in->rb_recv_ptr), free(in->rb_counts), free(in->rb_send_idx), free(in->rb_recv_src), free(in->rb_recv_idx);
+    free(in->bg_blockptr), free(in->bg_blockrows), free(in->bg_colors);
+    memset(in, 0, sizeof *in); /* the borrowed matrices with them */
+  }
 }
 
 pmg_status pmg_mgmc_destroy(pmg_mgmc *hp)
@@ -1057,8 +1082,6 @@ pmg_status pmg_mgmc_destroy(pmg_mgmc *hp)
     pmg_distmcsor_destroy(&Lv->dm);
     pmg_mcsor_destroy(&Lv->mc);
     pmg_blockgibbs_destroy(&Lv->bg);
-    free(Lv->bg_blockptr), free(Lv->bg_blockrows), free(Lv->bg_colors);
-    free(Lv->rb_colors), free(Lv->rb_send_ptr), free(Lv->rb_recv_ptr), free(Lv->rb_counts), free(Lv->rb_send_idx), free(Lv->rb_recv_src), free(Lv->rb_recv_idx);
     pmg_dev_free(Lv->b);
     pmg_dev_free(Lv->x);
     pmg_dev_free(Lv->r);
@@ -1081,11 +1104,9 @@ pmg_status pmg_mgmc_destroy(pmg_mgmc *hp)
     pmg_dev_free(Lv->R_val);
     pmg_hcsr_free(&Lv->A_host);
     pmg_hcsr_free(&Lv->P_host);
-    free(Lv->A_rp_own);
-    free(Lv->A_ci_own);
-    free(Lv->P_rp_own);
-    free(Lv->P_ci_own);
   }
+  pmg_mgmc_i_free_inputs(h);
+  free(h->in);
   pmg_mgmc_i_free_chains(h);
   pmg_chol_destroy(&h->chol);
   pmg_dev_free(h->y_lay);
