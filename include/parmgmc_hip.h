@@ -831,16 +831,31 @@ pmg_status pmg_chainstats_iact(pmg_chainstats cs, int32_t q, int32_t first, int3
    var = 1 / q + M2 / (N - 1) with the two quotients and the sum rounded as written.  No floating-point atomics: the order of
    every sum is fixed by (matrix, nchains) alone, whatever the stream and the calls before (kernels_rbstats.hip).
    Creation and all argument checks touch no device; device memory, the matrix upload included, is allocated by the first
-   update or cond_mean.  Single device; one right-hand side shared by all chains; a grid (DMDA) operator is passed as its
-   assembled CSR.  Work is enqueued on `stream` and not synchronised, except where a call returns host data or says so; the
-   first update or cond_mean after creation or after pmg_rbstats_set_lowrank allocates and uploads, which is synchronous.
+   update or cond_mean.  Single device; one right-hand side shared by all chains.  Work is enqueued on `stream` and not
+   synchronised, except where a call returns host data or says so; the first update or cond_mean after creation or after
+   pmg_rbstats_set_lowrank allocates and uploads, which is synchronous.
    Algorithmic bytes of one update: 12 nnz + 8 n C + 48 n (the matrix; Y once, neighbour gathers counted as cache hits; b, q,
-   mean and M2 read and written), with a low-rank term + 8 n k + 8 n C (pmg_rbstats_get_algorithmic_bytes). */
+   mean and M2 read and written), with a low-rank term + 8 n k + 8 n C (pmg_rbstats_get_algorithmic_bytes).
+   A grid (DMDA) operator is either passed as its assembled CSR or, matrix-free, as (nx, ny, nz, kappa) to
+   pmg_rbstats_create_dmda: the same handle type, every entry point below works on it unchanged, and it returns the bits of the
+   CSR handle on the assembled operator (kernels_rbstats_dmda.hip).  Its update reads no matrix, b only where one
+   is set and q only with a low-rank term: 8 n C + 32 n, + 8 n with a right-hand side, + 8 n + 8 n k + 8 n C with a low-rank
+   term.  A DMDA handle is single device too: a z-slab sampler hands its callback the rows of its slab, fewer than the handle
+   has, and the callbacks refuse that with PMG_ERR_ARG_SIZ. */
 typedef struct pmg_rbstats_s *pmg_rbstats;
 /* The matrix (host CSR, 32-bit indices, natural numbering) is copied.  PMG_ERR_ARG_OUTOFRANGE: n < 1, nchains < 1, a column
    outside [0, n); PMG_ERR_ARG_WRONG, the code of pmg_mcsor_setup for a row without a stored diagonal entry: such a row, a
    diagonal entry stored twice, a diagonal entry <= 0 or not finite, a rowptr that is not monotone. */
 pmg_status pmg_rbstats_create_csr(int32_t n, const int32_t *rowptr_host, const int32_t *colidx_host, const double *vals_host, int32_t nchains, pmg_rbstats *rb);
+/* The operator of pmg_grid_create, pmg_mat_create_dmda and pmg_mgmc_create_dmda (MatAssembleShiftedLaplaceFD,
+   src/problems.c:14-75, and its 3-D analogue; nz = 1 is the reference's 2-D matrix) on n = nx ny nz rows in DMDA natural order,
+   i fastest, without a matrix: hinv2 = 1.0 / ((nx - 1) * (nx - 1)), a_ii = kappa * kappa + hinv2 per in-domain neighbour (by
+   repeated addition), off-diagonal entries -hinv2 in the order (k-1) (j-1) (i-1) (i+1) (j+1) (k+1).  Y is n x nchains, chain
+   fastest, natural rows (what pmg_sample_callback hands over at nchains = 1); B of pmg_rbstats_set_lowrank is n x k in natural
+   numbering (what pmg_make_observation_mats_dmda returns).  Checks in this order: PMG_ERR_ARG_NULL (rb);
+   PMG_ERR_ARG_OUTOFRANGE: nx < 2, ny < 1 or nz < 1 (as pmg_mat_create_dmda), nx ny nz > INT32_MAX, nchains < 1;
+   PMG_ERR_ARG_WRONG: a kappa whose square is not finite. */
+pmg_status pmg_rbstats_create_dmda(int32_t nx, int32_t ny, int32_t nz, double kappa, int32_t nchains, pmg_rbstats *rb);
 pmg_status pmg_rbstats_destroy(pmg_rbstats *rb);
 /* Q = A + B S B^T: B is n x k column-major on the host in the matrix's row numbering, S the k diagonal entries (the arguments
    of pmg_mcsor_set_lowrank; both copied); k = 0 removes the term.  Forgets the recorded statistics (as pmg_rbstats_reset).

@@ -298,6 +298,7 @@ _sig = {
     "pmg_iact_chains": (_int, [_i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pmg_chainstats_iact": (_int, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
     "pmg_rbstats_create_csr": (_int, [_i32, _vp, _vp, _vp, _i32, C.POINTER(_vp)]),
+    "pmg_rbstats_create_dmda": (_int, [_i32, _i32, _i32, _dbl, _i32, C.POINTER(_vp)]),
     "pmg_rbstats_destroy": (_int, [C.POINTER(_vp)]),
     "pmg_rbstats_set_lowrank": (_int, [_vp, _i32, _vp, _vp]),
     "pmg_rbstats_set_rhs": (_int, [_vp, _vp]),

@@ -258,6 +258,21 @@ int  pmgk_rbstats_update(const pmgk_rbstats_op *A, int32_t nchains, double count
 int  pmgk_rbstats_cond_mean(const pmgk_rbstats_op *A, int32_t nchains, const double *Y, double *M, void *stream);
 int  pmgk_rbstats_fields(int64_t n, double count, const double *q, const double *mean, const double *M2, double *mean_out, double *var_out, void *stream);
 
+/* The same on the DMDA operator of pmg_grid_create, matrix-free (kernels_rbstats_dmda.hip): nx ny nz <= INT32_MAX rows in
+   natural order, kk = kappa * kappa and hinv2 = 1.0 / ((nx - 1) * (nx - 1)) formed on the host.  q is read only with k > 0
+   (without a low-rank term the kernel forms it in registers); b, k, B, S, T as in pmgk_rbstats_op.  pmgk_rbstats_dmda_geometry
+   is the only source of the launch geometry: with one chain *iters planes per wavefront, otherwise pmgk_rbstats_geometry's. */
+typedef struct {
+  int32_t       nx, ny, nz;
+  double        kk, hinv2;
+  const double *q, *b;
+  int           k;
+  const double *B, *S, *T;
+} pmgk_rbstats_dmda_op;
+void pmgk_rbstats_dmda_geometry(int32_t nx, int32_t ny, int32_t nz, int32_t nchains, int32_t *iters, int32_t *nblocks);
+int  pmgk_rbstats_dmda_update(const pmgk_rbstats_dmda_op *A, int32_t nchains, double count, const double *Y, double *mean, double *M2, void *stream);
+int  pmgk_rbstats_dmda_cond_mean(const pmgk_rbstats_dmda_op *A, int32_t nchains, const double *Y, double *M, void *stream);
+
 /* covariance over the chains (kernels_chaincov.hip): Y is n x K, k fastest; Sigma and Cout n x n row-major; partial holds
    pmgk_chaincov_ntiles(n) doubles, one per 32 x 32 tile of the lower triangle; every sum in an order that (n, K) alone fixes */
 int pmgk_chaincov_ntiles(int32_t n);

@@ -6,9 +6,18 @@
  * diagonal apart), the low-rank factors, and mean and M2 (n doubles each) on the device.  Creation and every argument check run
  * without a device; device memory, the matrix upload included, is allocated by the first update or cond_mean.  The arithmetic
  * and its order are stated in kernels_rbstats.hip.
+ * A DMDA handle (pmg_rbstats_create_dmda) holds no matrix: the operator of pmg_grid_create is (nx, ny, nz, kappa), its diagonal
+ * comes from rb_diag and the launches go to kernels_rbstats_dmda.hip, which gives the bits of the CSR kernel on the assembled
+ * operator.  Everything that does not touch the matrix is one copy for both kinds.
  */
 #include <math.h>
 #include "pmg_internal.h"
+
+/* Weak references: this file is also linked, without the kernels, into host-only programs that bring launchers of their own for
+   the CSR kernels only (tests/sanitize/rbstats_san.c).  The library always holds kernels_rbstats_dmda.hip; where the two
+   launchers are absent a DMDA handle's update and cond_mean fail with PMG_ERR_SUP (rb_launch), they do not fall back. */
+extern int pmgk_rbstats_dmda_update(const pmgk_rbstats_dmda_op *A, int32_t nchains, double count, const double *Y, double *mean, double *M2, void *stream) __attribute__((weak));
+extern int pmgk_rbstats_dmda_cond_mean(const pmgk_rbstats_dmda_op *A, int32_t nchains, const double *Y, double *M, void *stream) __attribute__((weak));
 
 struct pmg_rbstats_s {
   int64_t n, nnz; /* nnz: stored entries of the matrix as given, the diagonal included */
@@ -22,7 +31,24 @@ struct pmg_rbstats_s {
   int32_t *rowptr, *cols;
   double  *vals, *q, *B, *S, *T, *partial, *mean, *M2;
   int      allocated, lr_dirty; /* lr_dirty: q / B / S on the device are not the host's */
+  /* a DMDA handle: no rowptr / cols / vals / diag_h; kk = kappa * kappa, hinv2 = 1.0 / ((nx - 1) * (nx - 1)) */
+  int     dmda;
+  int32_t nx, ny, nz;
+  double  kk, hinv2;
 };
+
+/* a_rr: the stored diagonal entry, or that of MatAssembleShiftedLaplaceFD (kappa * kappa, then + hinv2 once per in-domain
+   neighbour by repeated addition; the addends are equal, so the order of the neighbours does not matter) */
+static double rb_diag(const struct pmg_rbstats_s *h, size_t r)
+{
+  if (!h->dmda) return h->diag_h[r];
+  const size_t  P = (size_t)h->nx * (size_t)h->ny;
+  const int32_t k = (int32_t)(r / P), j = (int32_t)((r % P) / (size_t)h->nx), i = (int32_t)(r % (size_t)h->nx);
+  const int     cnt = (k > 0) + (j > 0) + (i > 0) + (k < h->nz - 1) + (j < h->ny - 1) + (i < h->nx - 1);
+  double        d   = h->kk;
+  for (int a = 0; a < cnt; ++a) d += h->hinv2;
+  return d;
+}
 
 pmg_status pmg_rbstats_destroy(pmg_rbstats *rb)
 {
@@ -93,6 +119,34 @@ pmg_status pmg_rbstats_create_csr(int32_t n, const int32_t *rowptr, const int32_
   return PMG_SUCCESS;
 }
 
+/* The operator of pmg_grid_create / pmg_mat_create_dmda / pmg_mgmc_create_dmda on an nx x ny x nz vertex grid (nz = 1: the
+   reference's 2-D matrix), rows in DMDA natural order, matrix-free.  The size checks of pmg_mat_create_dmda, then
+   nx ny nz <= INT32_MAX and nchains >= 1. */
+pmg_status pmg_rbstats_create_dmda(int32_t nx, int32_t ny, int32_t nz, double kappa, int32_t nchains, pmg_rbstats *rb)
+{
+  PMG_CHECK(rb, PMG_ERR_ARG_NULL, "null handle pointer");
+  *rb = NULL;
+  PMG_CHECK(nx >= 2 && ny >= 1 && nz >= 1, PMG_ERR_ARG_OUTOFRANGE, "grid %d x %d x %d", nx, ny, nz);
+  PMG_CHECK((int64_t)nx * ny <= INT32_MAX && (int64_t)nx * ny * nz <= INT32_MAX, PMG_ERR_ARG_OUTOFRANGE, "grid %d x %d x %d has more than %d points", nx, ny, nz, INT32_MAX);
+  const int64_t n = (int64_t)nx * ny * nz;
+  PMG_CALL(pmg_chains_size_check(n, nchains));
+  PMG_CHECK(isfinite(kappa * kappa), PMG_ERR_ARG_WRONG, "kappa = %g: a conditional precision must be positive and finite", kappa);
+  pmg_rbstats h = (pmg_rbstats)calloc(1, sizeof(*h));
+  PMG_CHECK(h, PMG_ERR_MEM, "out of memory");
+  h->dmda = 1, h->nx = nx, h->ny = ny, h->nz = nz;
+  h->n = n, h->C = nchains, h->nnz = 0;
+  h->kk    = kappa * kappa;
+  h->hinv2 = 1.0 / (double)((int64_t)(nx - 1) * (nx - 1)); /* the integer product first (src/problems.c:24) */
+  h->q_h   = (double *)malloc(sizeof(double) * (size_t)n);
+  if (!h->q_h) {
+    pmg_rbstats_destroy(&h);
+    return pmg_set_error(PMG_ERR_MEM, __FILE__, __LINE__, "out of memory");
+  }
+  for (size_t r = 0; r < (size_t)n; ++r) h->q_h[r] = rb_diag(h, r);
+  *rb = h;
+  return PMG_SUCCESS;
+}
+
 /* Q = A + B S B^T: B n x k column-major in the matrix's row numbering, S the k diagonal entries (as pmg_mcsor_set_lowrank);
    q_i = a_ii + sum_k S_k * (B_ik * B_ik), k ascending.  k = 0 removes the term. */
 pmg_status pmg_rbstats_set_lowrank(pmg_rbstats h, int32_t k, const double *B_host, const double *S_host)
@@ -102,7 +156,7 @@ pmg_status pmg_rbstats_set_lowrank(pmg_rbstats h, int32_t k, const double *B_hos
   PMG_CHECK(k == 0 || (B_host && S_host), PMG_ERR_ARG_NULL, "null low-rank factor");
   const size_t n = (size_t)h->n;
   for (size_t r = 0; r < n; ++r) { /* before anything changes */
-    double q = h->diag_h[r];
+    double q = rb_diag(h, r);
     for (int32_t j = 0; j < k; ++j) q = q + S_host[j] * (B_host[r + n * (size_t)j] * B_host[r + n * (size_t)j]);
     PMG_CHECK(isfinite(q) && q > 0.0, PMG_ERR_ARG_WRONG, "row %zu has the conditional precision %g with the low-rank term: it must be positive and finite", r, q);
   }
@@ -118,7 +172,7 @@ pmg_status pmg_rbstats_set_lowrank(pmg_rbstats h, int32_t k, const double *B_hos
   free(h->B_h);
   h->B_h = B, h->k = k;
   for (size_t r = 0; r < n; ++r) {
-    double q = h->diag_h[r];
+    double q = rb_diag(h, r);
     for (int32_t j = 0; j < k; ++j) q = q + h->S_h[j] * (B[r + n * (size_t)j] * B[r + n * (size_t)j]);
     h->q_h[r] = q;
   }
@@ -164,24 +218,32 @@ pmg_status pmg_rbstats_get_cond_precision(pmg_rbstats h, double *q_host)
 }
 
 /* the matrix (12 bytes per stored entry), Y once (neighbour gathers counted as cache hits), b, q, and mean / M2 read and
-   written; with a low-rank term B, and Y once more for B^T Y */
+   written; with a low-rank term B, and Y once more for B^T Y.  A DMDA handle reads no matrix, b only where one is set and q
+   only with a low-rank term (kernels_rbstats_dmda.hip forms it in registers otherwise). */
 pmg_status pmg_rbstats_get_algorithmic_bytes(pmg_rbstats h, double *bytes)
 {
   PMG_CHECK(h && bytes, PMG_ERR_ARG_NULL, "null argument");
+  if (h->dmda) {
+    *bytes = 8.0 * (double)h->n * h->C + 32.0 * (double)h->n + (h->b_dev ? 8.0 * (double)h->n : 0.0);
+    if (h->k > 0) *bytes += 8.0 * (double)h->n + 8.0 * (double)h->n * h->k + 8.0 * (double)h->n * h->C;
+    return PMG_SUCCESS;
+  }
   *bytes = 12.0 * (double)h->nnz + 8.0 * (double)h->n * h->C + 48.0 * (double)h->n;
   if (h->k > 0) *bytes += 8.0 * (double)h->n * h->k + 8.0 * (double)h->n * h->C;
   return PMG_SUCCESS;
 }
 
-static pmg_status rb_prepare(pmg_rbstats h, pmgk_rbstats_op *A, void *stream)
+static pmg_status rb_prepare(pmg_rbstats h, void *stream)
 {
   const size_t n = (size_t)h->n;
   if (!h->allocated) {
-    PMG_CALL(pmg_dev_upload((void **)&h->rowptr, h->rowptr_h, sizeof(int32_t) * (n + 1)));
-    const size_t nz = (size_t)h->rowptr_h[n];
-    if (nz) {
-      PMG_CALL(pmg_dev_upload((void **)&h->cols, h->cols_h, sizeof(int32_t) * nz));
-      PMG_CALL(pmg_dev_upload((void **)&h->vals, h->vals_h, sizeof(double) * nz));
+    if (!h->dmda) {
+      PMG_CALL(pmg_dev_upload((void **)&h->rowptr, h->rowptr_h, sizeof(int32_t) * (n + 1)));
+      const size_t nz = (size_t)h->rowptr_h[n];
+      if (nz) {
+        PMG_CALL(pmg_dev_upload((void **)&h->cols, h->cols_h, sizeof(int32_t) * nz));
+        PMG_CALL(pmg_dev_upload((void **)&h->vals, h->vals_h, sizeof(double) * nz));
+      }
     }
     PMG_CALL(pmg_dev_alloc((void **)&h->q, sizeof(double) * n));
     PMG_CALL(pmg_dev_alloc((void **)&h->mean, sizeof(double) * n));
@@ -203,8 +265,24 @@ static pmg_status rb_prepare(pmg_rbstats h, pmgk_rbstats_op *A, void *stream)
     }
     h->lr_dirty = 0;
   }
-  const pmgk_rbstats_op op = {h->n, h->rowptr, h->cols, h->vals, h->q, h->b_dev, h->k, h->B, h->S, h->T};
-  *A                       = op;
+  return PMG_SUCCESS;
+}
+
+/* the fused launch of one step on a prepared handle: M_dev = NULL merges the moments of the conditional means, otherwise they
+   are stored there */
+static pmg_status rb_launch(pmg_rbstats h, const double *Y_dev, double *M_dev, void *stream)
+{
+  const double count = (double)h->steps * (double)h->C;
+  if (h->dmda) {
+    PMG_CHECK(pmgk_rbstats_dmda_update && pmgk_rbstats_dmda_cond_mean, PMG_ERR_SUP, "this program was linked without kernels_rbstats_dmda.hip");
+    const pmgk_rbstats_dmda_op A = {h->nx, h->ny, h->nz, h->kk, h->hinv2, h->q, h->b_dev, h->k, h->B, h->S, h->T};
+    if (M_dev) PMG_KERNEL(pmgk_rbstats_dmda_cond_mean(&A, h->C, Y_dev, M_dev, stream));
+    else PMG_KERNEL(pmgk_rbstats_dmda_update(&A, h->C, count, Y_dev, h->mean, h->M2, stream));
+    return PMG_SUCCESS;
+  }
+  const pmgk_rbstats_op A = {h->n, h->rowptr, h->cols, h->vals, h->q, h->b_dev, h->k, h->B, h->S, h->T};
+  if (M_dev) PMG_KERNEL(pmgk_rbstats_cond_mean(&A, h->C, Y_dev, M_dev, stream));
+  else PMG_KERNEL(pmgk_rbstats_update(&A, h->C, count, Y_dev, h->mean, h->M2, stream));
   return PMG_SUCCESS;
 }
 
@@ -220,10 +298,9 @@ pmg_status pmg_rbstats_update(pmg_rbstats h, const double *Y_dev, void *stream)
   PMG_CHECK(h, PMG_ERR_ARG_NULL, "null handle");
   PMG_CHECK(Y_dev, PMG_ERR_ARG_NULL, "null sample array");
   PMG_CHECK(h->steps < INT32_MAX, PMG_ERR_ARG_OUTOFRANGE, "the step count is full");
-  pmgk_rbstats_op A;
-  PMG_CALL(rb_prepare(h, &A, stream));
+  PMG_CALL(rb_prepare(h, stream));
   PMG_CALL(rb_bty(h, Y_dev, stream));
-  PMG_KERNEL(pmgk_rbstats_update(&A, h->C, (double)h->steps * (double)h->C, Y_dev, h->mean, h->M2, stream));
+  PMG_CALL(rb_launch(h, Y_dev, NULL, stream));
   h->steps++;
   return PMG_SUCCESS;
 }
@@ -233,10 +310,9 @@ pmg_status pmg_rbstats_cond_mean(pmg_rbstats h, const double *Y_dev, double *M_d
   PMG_CHECK(h, PMG_ERR_ARG_NULL, "null handle");
   PMG_CHECK(Y_dev && M_dev, PMG_ERR_ARG_NULL, "null sample or output array");
   PMG_CHECK(Y_dev != M_dev, PMG_ERR_ARG_WRONG, "the conditional means cannot overwrite the samples they are gathered from");
-  pmgk_rbstats_op A;
-  PMG_CALL(rb_prepare(h, &A, stream));
+  PMG_CALL(rb_prepare(h, stream));
   PMG_CALL(rb_bty(h, Y_dev, stream));
-  PMG_KERNEL(pmgk_rbstats_cond_mean(&A, h->C, Y_dev, M_dev, stream));
+  PMG_CALL(rb_launch(h, Y_dev, M_dev, stream));
   return PMG_SUCCESS;
 }
 

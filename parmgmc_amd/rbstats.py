@@ -38,6 +38,21 @@ class RBStats:
             self.set_lowrank(*lowrank)
         self.set_rhs(b)
 
+    @classmethod
+    def dmda(cls, nx: int, ny: int, nz: int, kappa: float, nchains: int = 1, lowrank=None, b=None):
+        """pmg_rbstats_create_dmda: the same statistics on the grid operator of Grid / MGMC(nx, ny, nz, kappa), matrix-free, with
+        the bits of RBStats(oracle.shifted_laplace(nx, ny, nz, kappa)).  Rows in DMDA natural order (i fastest); lowrank = (B, S)
+        with B (n, k) in natural numbering (pmg_make_observation_mats_dmda); b as for the constructor."""
+        self = cls.__new__(cls)
+        self.n, self.nchains, self.k = int(nx) * int(ny) * int(nz), int(nchains), 0
+        self._h = C.c_void_p()
+        self._b = None
+        check(lib.pmg_rbstats_create_dmda(int(nx), int(ny), int(nz), float(kappa), self.nchains, C.byref(self._h)))
+        if lowrank is not None:
+            self.set_lowrank(*lowrank)
+        self.set_rhs(b)
+        return self
+
     def set_lowrank(self, B=None, S=None):
         """Q = A + B diag(S) B^T; B = None removes the term.  Forgets the recorded statistics."""
         if B is None:
